@@ -9,7 +9,14 @@ and with N > 1 GPUs the all-gather of the trajectories: pipelined
 beside the next rollout, or one RCCL all-gather after each rollout (--rccl-gather / fallback).
 value = E * T * K * N / max-over-ranks wall time. Inputs (scenes, windows) are resident in HBM.
 
-Also reported (same JSON line):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the line: metric / value / ms_per_step, the configuration and the roofline of the dominant kernel
+(from the HIP events of the last timed step; no run of its own). Scenes, initial policy and sampling
+keys are seeded, so the same arguments give the same inputs in every run; --dump-outputs DIR writes
+the last timed step's trajectory (dump_outputs) for output-by-output comparison of two builds.
+Every other leg below runs only with --full (the --no-* options then skip single legs).
+
+Reported in the same JSON line (all but `roofline` need --full):
   roofline      dominant kernel = k_rollout_steps (per-step figures: its launch / T); peak = the MFMA
                 peak of its FLOP mix (the encoder GEMMs as fp32-accurate split products on the f16
                 cores at 16/3 x the f32 MFMA rate, embeddings and heads on the f32 MFMA);
@@ -264,7 +271,7 @@ def env_bytes_per_step(M):
     return 24 * M + 490
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -297,7 +304,60 @@ def parse():
                     help="one fused launch per rollout step instead of one launch per iteration")
     ap.add_argument("--full-window", action="store_true",
                     help="policy forward over the full window every step (no window-row ring)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (env differential and phase share, "
+                         "env-only launches, K1, the PPO update legs, end-to-end iterations, the drop-in loop, the "
+                         "CPU baselines, the N > 1 timeline); the --no-* options then skip single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the trajectory of the last timed step to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; see dump_outputs)")
+    return plain_unless_full(ap.parse_args(argv))
+
+
+def plain_unless_full(args):
+    """Without --full a run only sets up, warms up, times its steps and prints the line: every leg
+    that measures or checks something else is switched off, whatever the --no-* options say."""
+    if not args.full:
+        args.no_ppo = args.no_env_fused = args.no_cpu_baseline = args.no_e2e = True
+        args.no_env_diff = args.no_dropin = True
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # of the 64 MB a dump may take; the .npy headers are a few hundred bytes
+DUMP_SEED = 20240
+
+
+def trajectory_outputs(traj):
+    """What a caller of RolloutEngine.collect() receives: the iteration's trajectory buffers, time-major
+    [T, E, ...] (obs [T + 1, E, 5, 14]: obs[T] is the next iteration's first window; last_values [1, E]:
+    the bootstrap V(s_T)), with the GAE returns and (normalised) advantages."""
+    outs = {"obs": traj.obs, "actions": traj.actions, "logp": traj.logp, "values": traj.values,
+            "rewards": traj.rewards, "dones": traj.dones, "last_values": traj.last_values.reshape(1, -1),
+            "returns": traj.ret, "advantages": traj.adv}
+    if traj.info is not None:
+        outs["info"] = traj.info
+    return outs
+
+
+def dump_outputs(dirname, outs, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Write each tensor of `outs` ([T, E, ...], env axis 1) as dirname/<name>.npy: float64 tensors as
+    float64, every other dtype as float32 (int8 actions and uint8 done flags convert exactly). Every
+    array gets an equal share of `budget`; one that is larger keeps a fixed sample of its envs: the
+    first k of numpy's default_rng(seed).permutation(E), in ascending order, k the most that fit --
+    the same envs for the same shapes in every run. Returns {name: (shape, dtype, envs kept)}."""
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(1, len(outs))
+    written = {}
+    for name, t in outs.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        E = a.shape[1]
+        if a.nbytes > share:
+            k = max(1, share // (a.nbytes // E))
+            a = a[:, np.sort(np.random.default_rng(seed).permutation(E)[:k])]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = (a.shape, str(a.dtype), a.shape[1])
+    return written
 
 
 def cpu_baseline(args, state_dict, seconds):
@@ -909,6 +969,9 @@ def main():
     env_steps = E * T * args.steps * world
     value = env_steps / elapsed
 
+    if args.dump_outputs and rank == 0:  # before any later leg runs another rollout or an update
+        dump_outputs(args.dump_outputs, trajectory_outputs(eng.traj))
+
     exchange = None
     if dist is not None:  # the exchange used, how it was chosen, and the pipelined copies checked
         pipelined = iteration is it_pipelined
@@ -921,7 +984,7 @@ def main():
                                    "payloads, bitwise, every rank") if xchg is not None else None}
 
     timeline = None
-    if dist is not None:  # one more iteration, untimed, with the phases separated: rollout | exchange
+    if dist is not None and args.full:  # one more iteration, untimed, with the phases separated: rollout | exchange
         torch.cuda.synchronize()
         dist.barrier()
         a = time.perf_counter()
@@ -1073,6 +1136,7 @@ def main():
             "metric": "env-steps/sec (whole node), full PPO rollout, 4096 envs x 16 UAV x 32 tgt per GPU",
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "full": args.full,
             "vs_baseline": None, "dtype": "f32 policy (f32 MFMA + fp32-accurate split products on the f16 MFMA) + f64 env",
             "data": "synthetic (on-device Philox scenes, "
             "random-init policy, actions sampled from the policy)",

@@ -9,7 +9,7 @@ rc=$?
 grep -E "PASSED|FAILED|ERROR|passed|failed|^E  " gpurun_out/pytest_dist.log | tail -30
 [ $rc -eq 0 ] || exit $rc
 BENCH_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full \
   > gpurun_out/bench_gloo2.json 2> gpurun_out/bench_gloo2.err || { tail -30 gpurun_out/bench_gloo2.err; exit 1; }
 python -c "
 import json; d=json.loads(open('gpurun_out/bench_gloo2.json').read().strip().splitlines()[-1])

@@ -31,6 +31,7 @@ if [ -z "$SKIP_PROFILES" ]; then
   mkdir -p gpurun_out/profiles_$TAG
   cp profiles/${TAG}_* gpurun_out/profiles_$TAG/
 fi
+BENCH_ARGS="--full $BENCH_ARGS"  # every leg of the line, not the headline alone
 timeout -k 10 900 python bench.py $BENCH_ARGS > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -20 gpurun_out/bench_$TAG.err; exit 1; }
 echo bench ok
 python - "$TAG" <<'EOF'

@@ -10,6 +10,8 @@ eval timeout -k 10 900 python -u -m pytest tests -m gpu -v -s --timeout 300 --ti
 rc=$?
 grep -E "^(FAILED|ERROR)|passed|failed" gpurun_out/pytest_$TAG.log | tail -15
 [ $rc -le 1 ] || { tail -40 gpurun_out/pytest_$TAG.log; exit $rc; }
+# --full with all but the env differential / phase share skipped (read below)
+BENCH_ARGS=${BENCH_ARGS:---full --no-ppo --no-e2e --no-dropin --no-cpu-baseline --no-env-fused}
 timeout -k 10 600 python bench.py ${BENCH_ARGS:---no-ppo --no-e2e --no-dropin --no-cpu-baseline --no-env-fused} > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || { tail -20 gpurun_out/bench_$TAG.err; exit 1; }
 python -c "
 import json; d=json.loads(open('gpurun_out/bench_$TAG.json').read().strip().splitlines()[-1]); r=d['roofline']

@@ -4,7 +4,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-A="--steps 2 --warmup 1 --no-env-fused --no-cpu-baseline --no-e2e --no-env-diff --no-dropin"
+A="--steps 2 --warmup 1 --full --no-env-fused --no-cpu-baseline --no-e2e --no-env-diff --no-dropin"
 for r in 1 2 3; do
   for b in base v_prev; do
     if [ $b = base ]; then unset UAVHIP_LIB UAVHIP_ACCEPT_PREV_ABI; else export UAVHIP_LIB=$GRAFT_REPO_ROOT/scripts/$b/libuavhip.so UAVHIP_ACCEPT_PREV_ABI=1; fi

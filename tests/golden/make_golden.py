@@ -22,6 +22,8 @@ Outputs (all numpy .npz, loaded with allow_pickle=False):
                  train()'s own frame, its CSV rows (:161-195) and the update losses behind them
   init_rng.npz   the sampler's first torch.randperm after PPOAgent() / two networks under
                  torch.manual_seed (the CPU generator's position after construction)
+  saved_models.json  keys, shapes and dtypes of the state_dicts in saved_models/*/best_model.pth
+                 (`... saved_models` writes only this file)
 
 Usage:  python tests/golden/make_golden.py   (takes ~1 min on CPU; `... init_rng` writes only init_rng.npz)
 """
@@ -539,11 +541,29 @@ def gen_main_train(episodes=30):
             "episode_fields": np.array(json.dumps(["episode"] + list(EP_LOCALS))), "meta": np.array(json.dumps(meta()))}
 
 
+# ----------------------------------------------------------------------------- shipped checkpoints
+def gen_saved_models():
+    """What the reference's saved_models/*/best_model.pth files hold, without their weights (2.4 MB
+    each): per file, every state_dict key with its shape and dtype, in file order."""
+    import glob
+    files = {}
+    for path in sorted(glob.glob(os.path.join(REF, "saved_models", "*", "best_model.pth"))):
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        rel = os.path.relpath(path, os.path.join(REF, "saved_models"))
+        files[rel] = [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()]
+    return {"files": files, "meta": {k: v for k, v in meta().items() if k != "reference"}}
+
+
 def main():
     outdir = HERE
     torch.set_num_threads(min(8, os.cpu_count() or 1))
     if sys.argv[1:] == ["init_rng"]:  # the one fixture added in round 3
         np.savez_compressed(os.path.join(outdir, "init_rng.npz"), **gen_init_rng())
+        return
+    with open(os.path.join(outdir, "saved_models.json"), "w") as f:
+        json.dump(gen_saved_models(), f)
+        f.write("\n")
+    if sys.argv[1:] == ["saved_models"]:
         return
     np.savez_compressed(os.path.join(outdir, "mechanics.npz"), **gen_mechanics(np.random.default_rng(3)))
     np.savez_compressed(os.path.join(outdir, "scenes.npz"), **gen_scenes())

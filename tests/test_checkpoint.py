@@ -2,7 +2,7 @@
 the reference's torch.save(state_dict) files round-trip through the HIP policy, and the older
 architectures of saved_models/*/best_model.pth are recognised, refused by a strict load and
 partially loaded with a report by a non-strict one. CPU, and one GPU test of the repack."""
-import glob
+import json
 import os
 
 import pytest
@@ -11,7 +11,7 @@ import torch
 from uavhip.checkpoint import describe, load_checkpoint, read_checkpoint, save_checkpoint
 from uavhip.policy import TransformerActorCritic
 
-REF_MODELS = "/root/reference/saved_models"
+SAVED_MODELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "saved_models.json")
 
 
 def _legacy(kind, seed=3):
@@ -94,12 +94,23 @@ def test_not_a_state_dict(tmp_path):
         read_checkpoint(str(tmp_path / "missing.pth"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference checkpoints not present (GPU box)")
-def test_reference_saved_models_are_recognised():
-    """The four files shipped with the reference (read with weights_only=True): SURVEY.md §2."""
+def test_reference_saved_models_are_recognised(tmp_path):
+    """The four files shipped with the reference, rebuilt from the recorded keys,
+    shapes and dtypes of their state_dicts (tests/golden/saved_models.json; the weights, 2.4 MB a
+    file, are not kept: describe() reads names and shapes only), saved in the reference's format and
+    read back with weights_only=True."""
+    with open(SAVED_MODELS) as fh:
+        files = json.load(fh)["files"]
+    assert len(files) == 4
     seen = {}
-    for path in sorted(glob.glob(os.path.join(REF_MODELS, "*", "best_model.pth"))):
-        arch, f = describe(read_checkpoint(path))
+    for rel, entries in sorted(files.items()):
+        sd = {k: torch.zeros(shape, dtype=getattr(torch, dtype)) for k, shape, dtype in entries}
+        path = tmp_path / rel
+        path.parent.mkdir(parents=True)
+        torch.save(sd, str(path))
+        got = read_checkpoint(str(path))
+        assert list(got) == [k for k, _, _ in entries]
+        arch, f = describe(got)
         seen.setdefault(arch, []).append(f["params"])
     assert seen == {"flat640": [616003, 616003], "actor2": [551747, 551747]}
 
