@@ -7,8 +7,6 @@
 // backward therefore carries its gradients pre-scaled, BwdIO::gscale); from 65520 up the planes are
 // inf / -inf and every output that reads them is non-finite (common.hpp f16_lo; the ReLUs keep NaN,
 // relu_nan), never a finite wrong value.
-// (The notes below on tiles and layout date from the all-f32 design and still describe the f32
-// building blocks.)
 //
 // Work decomposition (MI355X-first):
 //  * one workgroup = 4 waves = 16 samples = 80 tokens, token index tok = s * 16 + p (s = window
@@ -65,7 +63,6 @@ constexpr int NTHR = NW * 64;
 constexpr int LDH = D + 8;      // 136: row stride = 2 mod 16 slots of 16 B -> the MFMA operand
                                 // reads/writes (lane = row i + 16 * k-group g) hit 16 distinct slots
 constexpr int LDB = 3 * 64 + 8; // 200: [Q 64 | K 64 | V 64] for a chunk of 4 heads
-constexpr int LDF = D + 8;
 constexpr int LDX = 16;         // input rows padded 14 -> 16 (one MFMA k-block)
 constexpr int LDZ = HID + 8;
 
@@ -269,50 +266,6 @@ __device__ __forceinline__ void gemm_tile(TID_F f32x4 (&acc)[CT], const APre<D>&
     }
 }
 template <int CT> constexpr int depth() { return CT == 1 ? 4 : 2; }
-
-// The same GEMM over the 7 k-blocks kb0, kb0 + 1, ... (mod 8) -- every block but kb0 - 1, which
-// the caller accumulated from registers (the wave's own LayerNorm output features, layer_tail).
-template <int D>
-__device__ __forceinline__ APre<D> prefetch_rot(TID_F const float* __restrict__ W, int ldw, int row, int kb0) {
-    const float* wp = frag_ptr(TID_C W, ldw, row, 0);
-    APre<D> r;
-#pragma unroll
-    for (int p = 0; p < D; ++p) r.a[p] = *reinterpret_cast<const f32x4*>(wp + 256 * ((kb0 + p) & (KB - 1)));
-    return r;
-}
-template <int CT, int D>
-__device__ __forceinline__ void gemm_tile_rot(TID_F f32x4 (&acc)[CT], const APre<D>& pre, const float* __restrict__ W,
-                                              int ldw, int row, const float* X, int ldx, int xtok0, int kb0) {
-    constexpr int NKB = KB - 1;
-    const int l = LANE(), i16 = l & 15, g = l >> 4;
-    const float* wp = frag_ptr(TID_C W, ldw, row, 0);
-    const float* xp[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) xp[ct] = X + (xtok0 + 16 * ct + i16) * ldx + 4 * g;
-    f32x4 a[NKB], b[NKB][CT];
-#pragma unroll
-    for (int p = 0; p < D; ++p) {
-        const int kb = (kb0 + p) & (KB - 1);
-        a[p] = pre.a[p];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) b[p][ct] = *reinterpret_cast<const f32x4*>(xp[ct] + 16 * kb);
-    }
-#pragma unroll
-    for (int i = 0; i < NKB; ++i) {
-        if (i + D < NKB) {
-            const int kb = (kb0 + i + D) & (KB - 1);
-            a[i + D] = *reinterpret_cast<const f32x4*>(wp + 256 * kb);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) b[i + D][ct] = *reinterpret_cast<const f32x4*>(xp[ct] + 16 * kb);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][j], b[i][ct][j], acc[ct], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 template <int CT>
 __device__ __forceinline__ void zero(f32x4 (&acc)[CT]) {
@@ -800,25 +753,11 @@ __device__ __forceinline__ void residual_layernorm(TID_F Smem& sm, const f32x4 (
     }
 }
 
-// Training mode: copy [tok][cols] rows from LDS (stride lds) to workspace rows (stride ldo, column
-// offset c0) for tokens [t0, t1), all 512 threads, float4 granules.
-__device__ __forceinline__ void store_rows(TID_F const float* src, int lds, float* dst, int ldo, int c0, int ncols, int t0,
-                                           int b0, bool compact, int t1 = TOK, bool nt = true) {
-#ifdef UAVHIP_EXP_NOSTORE  // timing experiment only (make NOSTORE=1): activations not written
-    return;
-#endif
-    const int n4 = ncols / 4, items = (t1 - t0) * n4;
-    for (int i = TIDX(); i < items; i += NTHR) {
-        const int tok = t0 + i / n4, q = i % n4;
-        act_st(dst + (size_t)orow(tok, b0, compact) * ldo + c0 + 4 * q, *reinterpret_cast<const f32x4*>(src + tok * lds + 4 * q), nt);
-    }
-}
-
 // Full-layer attention for heads [4c, 4c+4): one (sample, head, query group) task per 4 lanes,
 // each lane owning 4 of the 16 head dims; the task loads the 5 keys / values once for all its
 // queries (group 0: positions 0-2 on waves 0-3, group 1: positions 3-4 on waves 4-7).
 // attention_full_core leaves the outputs in registers (o[qi] for query position qs0 + qi, qi < nq);
-// attention_full_store writes them to sm.ctx (PLANES: as the split products' fp16 planes).
+// attention_full_store writes them to sm.ctx as the split products' fp16 planes.
 __device__ __forceinline__ void attention_full_core(TID_F Smem& sm, int c, f32x4 (&o)[3]) {
     const int q4 = TIDX() & 3, task = TIDX() >> 2;
     const int hh = task & 3, p = (task >> 2) & 15, grp = task >> 6;
@@ -858,9 +797,8 @@ __device__ __forceinline__ void attention_full_core(TID_F Smem& sm, int c, f32x4
         }
     }
 }
-// sc: the planes' scale (PLANES), of this thread's sample p (attn_sc)
-template <bool PLANES>
-__device__ __forceinline__ void attention_full_store(TID_F Smem& sm, int c, const f32x4 (&o)[3], float sc = 1.f) {
+// sc: the planes' scale, of this thread's sample p (att_sc)
+__device__ __forceinline__ void attention_full_store(TID_F Smem& sm, int c, const f32x4 (&o)[3], float sc) {
     const int q4 = TIDX() & 3, task = TIDX() >> 2;
     const int hh = task & 3, p = (task >> 2) & 15, grp = task >> 6;
     const int d0 = hh * HD + 4 * q4, qs0 = grp ? 3 : 0, nq = grp ? 2 : 3;
@@ -868,25 +806,18 @@ __device__ __forceinline__ void attention_full_store(TID_F Smem& sm, int c, cons
     for (int qi = 0; qi < 3; ++qi) {
         if (qi < nq) {
             const int ti = (qs0 + qi) * SPW + p;
-            if constexpr (PLANES) hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw(ti, 4 * c * HD + d0), o[qi] * sc);
-            else *reinterpret_cast<f32x4*>(sm.ctx + ti * LDH + 4 * c * HD + d0) = o[qi];
+            hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw(ti, 4 * c * HD + d0), o[qi] * sc);
         }
     }
 }
-// The planes' scale of an attention output of sample p (1 when it is stored in fp32)
-template <bool PLANES, int trunk, int layer>
-__device__ __forceinline__ float attn_sc(const Smem& sm, int p) {
-    if constexpr (PLANES) return att_sc<trunk, layer>(sm, p).sc;
-    else return 1.f;
-}
-// PLANES: the output goes to sm.ctx as the two fp16 planes of the split products (the out-projection's
+// The output goes to sm.ctx as the two fp16 planes of the split products (the out-projection's
 // operand), scaled for layer `layer` of trunk `trunk`.
 // (no defaults: every call site names the operand whose scale the planes carry -- ADVICE r05)
-template <bool PLANES, int trunk, int layer>
+template <int trunk, int layer>
 __device__ void attention_full(TID_F Smem& sm, int c, const float* __restrict__ P = nullptr) {
     f32x4 o[3];
     attention_full_core(TID_C sm, c, o);
-    attention_full_store<PLANES>(TID_C sm, c, o, attn_sc<PLANES, trunk, layer>(sm, (int)((TIDX() >> 4) & 15)));
+    attention_full_store(TID_C sm, c, o, att_sc<trunk, layer>(sm, (int)((TIDX() >> 4) & 15)).sc);
 }
 
 // Scaled-dot-product attention for heads [4c, 4c+4) of the query positions [qs0, qs0 + nqs) over
@@ -923,19 +854,17 @@ __device__ __forceinline__ void attention_task(TID_F Smem& sm, int task, int qs0
     o = f32x4{0.f, 0.f, 0.f, 0.f};
     att_mix(o, sc, inv, v);
 }
-template <bool PLANES>
-__device__ __forceinline__ void attention_out(TID_F Smem& sm, int c, int ti, int d0, const f32x4 o, float sc = 1.f) {
-    if constexpr (PLANES) hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw(ti, 4 * c * HD + d0), o * sc);
-    else *reinterpret_cast<f32x4*>(sm.ctx + ti * LDH + 4 * c * HD + d0) = o;
+__device__ __forceinline__ void attention_out(TID_F Smem& sm, int c, int ti, int d0, const f32x4 o, float sc) {
+    hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw(ti, 4 * c * HD + d0), o * sc);
 }
-template <bool PLANES, int trunk, int layer>
+template <int trunk, int layer>
 __device__ void attention_chunk(TID_F Smem& sm, int c, int qs0, int nqs, const float* __restrict__ P = nullptr) {
     const int ntask = nqs * SPW * 4;
     for (int task = TIDX() >> 2; task < ntask; task += NTHR / 4) {
         f32x4 o;
         int ti, d0;
         attention_task(TID_C sm, task, qs0, o, ti, d0);
-        attention_out<PLANES>(TID_C sm, c, ti, d0, o, attn_sc<PLANES, trunk, layer>(sm, ti & 15));
+        attention_out(TID_C sm, c, ti, d0, o, att_sc<trunk, layer>(sm, ti & 15).sc);
     }
 }
 
@@ -1021,67 +950,47 @@ __device__ __forceinline__ int kv_row(int wv, int c) { return (1 + (wv >> 2)) * 
 struct NoHook {
     __device__ void operator()() const {}
 };
-// Split-product paths of the inference forward (policy_layout.hpp kSplitParam): a full layer whose
-// out-projection and FFN run on the f16 cores, and a layer whose in_proj does (K / V / Q from the
-// fp16 planes of its input, which the previous layer's LN2 then writes).
+// Every layer's out-projection and FFN run as split products (policy_layout.hpp kSplitParam: every
+// layer GEMM weight has a split copy). A layer whose in_proj does too takes K / V / Q from the fp16
+// planes of its input, which the previous layer's LN2 then writes:
 template <int trunk, int layer>
-constexpr bool split_tail() {
-    return layer < 2 && split_slot(layer_param(trunk, layer, OUTW)) >= 0 && split_slot(layer_param(trunk, layer, L1W)) >= 0 &&
-           split_slot(layer_param(trunk, layer, L2W)) >= 0;
-}
-template <int trunk, int layer>
-constexpr bool split_inproj() {  // layer >= 1: its input comes from a split full layer's LN2 (layer 0's
-                                 // in_proj split copy serves the window-row ring only: split_ring)
+constexpr bool split_inproj() {  // layer >= 1: its input comes from a full layer's LN2 (layer 0's in_proj
+                                 // split copy serves the window-row ring and the training forward)
     return layer >= 1 && layer < 2 && split_slot(layer_param(trunk, layer, INW)) >= 0;
 }
-// The caller's prefetch of a layer tail's first out-projection weights / of a layer's first K/V
-// weights: the split copy's blocks on the split paths, the fp32 fragments otherwise. SP selects the
-// split paths: the inference forward always (SP = !TR), the training forward (TR) when its caller
-// asks (kTrainSplit); the position-split kernels (PSX) never.
-template <int trunk, int layer>
-constexpr bool split_l0() {  // layer 0's in_proj from the embedding's planes (the training forward)
-    return layer == 0 && split_slot(layer_param(trunk, 0, INW)) >= 0;
-}
-// Weight blocks (of 32 k) a split tail GEMM has in registers before its k-loop starts: the pruned
+// Weight blocks (of 32 k) a tail GEMM has in registers before its k-loop starts: the pruned
 // (one 16-token tile) tails of the inference forward take their whole tile (4 blocks) -- their MFMA
 // work per block is a fifth of a full layer's, far too little to cover an in-loop L2 round trip --
 // the rest 2 (EXP=74: the A/B build of the full-tile prefetch)
 constexpr bool kExpTailDepth4 = UAVHIP_EXP == 74;
 template <bool last, bool TR, int PSX>
 constexpr int tail_depth() { return kExpTailDepth4 && last && !TR && !PSX ? 4 : 2; }
-template <int trunk, int layer, bool last, bool TR, int PSX = 0, bool SP = !TR>
-using TailPre = std::conditional_t<SP && !PSX && split_tail<trunk, layer>(), HPre<tail_depth<last, TR, PSX>()>,
-                                   APre<depth<(last || PSX) ? 1 : S>()>>;
-template <int trunk, int layer, bool last, bool TR, bool SP = !TR>
-__device__ __forceinline__ TailPre<trunk, layer, last, TR, 0, SP> tail_prefetch(TID_F const float* __restrict__ P) {
+// The caller's prefetch of a layer tail's first out-projection weight blocks (layer_tail's `po`)
+template <bool last, bool TR, int PSX = 0>
+using TailPre = HPre<tail_depth<last, TR, PSX>()>;
+template <int trunk, int layer, bool last, bool TR>
+__device__ __forceinline__ TailPre<last, TR> tail_prefetch(TID_F const float* __restrict__ P) {
     const int wv = TIDX() >> 6;
-    if constexpr (SP && split_tail<trunk, layer>())
-        return hprefetch<tail_depth<last, TR, 0>()>(TID_C P, split_slot(layer_param(trunk, layer, OUTW)), D, 16 * wv, 0);
-    else
-        return prefetch<depth<last ? 1 : S>()>(TID_C P + kOffs.o[layer_param(trunk, layer, OUTW)], D, 16 * wv, 0);
+    return hprefetch<tail_depth<last, TR, 0>()>(TID_C P, split_slot(layer_param(trunk, layer, OUTW)), D, 16 * wv, 0);
 }
-template <int trunk, int layer, bool TR, bool SP = !TR>
+// Whether a layer's in_proj runs as split products (encoder_layer_split): when the previous layer's
+// LN2 wrote its input's planes, and for layer 0 of the training forward (the embedding's planes).
+// Otherwise -- layer 0 of the inference forward without the window-row ring -- it runs on the f32
+// MFMA (linear1). KvPre / kv_prefetch: the caller's prefetch of the layer's first K/V weight blocks.
+template <int trunk, int layer, bool TR>
 constexpr bool split_kv() {
-    return SP && (split_inproj<trunk, layer>() || (TR && split_l0<trunk, layer>()));
+    return split_inproj<trunk, layer>() || (TR && layer == 0);
 }
-template <int trunk, int layer, bool TR, bool SP = !TR>
-using KvPre = std::conditional_t<split_kv<trunk, layer, TR, SP>(), HPre<2>, APre<2>>;
-template <int trunk, int layer, bool TR, bool SP = !TR>
-__device__ __forceinline__ KvPre<trunk, layer, TR, SP> kv_prefetch(TID_F const float* __restrict__ P) {
+template <int trunk, int layer, bool TR>
+using KvPre = std::conditional_t<split_kv<trunk, layer, TR>(), HPre<2>, APre<2>>;
+template <int trunk, int layer, bool TR>
+__device__ __forceinline__ KvPre<trunk, layer, TR> kv_prefetch(TID_F const float* __restrict__ P) {
     const int wv = TIDX() >> 6;
-    if constexpr (split_kv<trunk, layer, TR, SP>())
+    if constexpr (split_kv<trunk, layer, TR>())
         return hprefetch<2>(TID_C P, split_slot(layer_param(trunk, layer, INW)), D, kv_row(wv, 0), 0);
     else
         return prefetch<2>(TID_C P + kOffs.o[layer_param(trunk, layer, INW)], D, kv_row(wv, 0), 0);
 }
-// The training forward's split switch (k_policy_forward<true>; the K7 kernels: kPsSplit below).
-constexpr bool kTrainSplit = true;
-
-// PSX (position split, the small-minibatch training step): a full (unpruned) layer computed for
-// the 16 tokens of ONE window position, column tile qt / 16, in [b * 5 + s] rows.
-template <int trunk, int layer, bool last, bool TR, class F = NoHook, int PSX = 0, bool SP = !TR>
-__device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restrict__ P, const TailPre<trunk, layer, last, TR, PSX, SP>& po,
-                           const TrainLayerIO& io, int b0, F pre_ln2 = F{}, int qt = 0);
 
 // Training mode: the Q|K|V of chunk c of the tokens [qtok0, 80) (Q) / all (K, V) from sm.big to qkv
 // rows, by waves 4-7 (less MFMA work than the K + Q waves sharing their SIMDs).
@@ -1127,169 +1036,25 @@ __device__ __forceinline__ float in_inv(const Smem& sm, int tok) {
     else return op_sc<trunk, layer - 1, kOpLn2>(sm).inv;
 }
 
-// An encoder layer whose in_proj runs as split products: K / V of all 80 tokens and Q of the query
-// tokens from the fp16 planes of the layer input, fp32 Q | K | V into sm.big, then attention and
-// the layer tail. The input planes are
-//   layer >= 1: in sm.h (the previous layer's LN2 wrote them, and its position-4 rows in fp32 to
-//               sm.ctx rows 0-15: the residual of this pruned layer);
-//   layer 0 (training forward): in sm.ctx (the embedding wrote them beside its fp32 rows in sm.h) --
-//               so chunk 0's attention output waits in registers until chunk 1's GEMMs have read
-//               sm.ctx, then both chunks are written.
-template <int trunk, int layer, bool last, bool TR, class F = NoHook>
-__device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float* __restrict__ P, HPre<2> pkv,
-                                                    const TrainLayerIO& io, int b0, F pre_ln2) {
-    [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
-    PTR(tb);
-    constexpr int si = split_slot(layer_param(trunk, layer, INW));
-    constexpr int CTQ = last ? 1 : S, qtok0 = last ? (S - 1) * SPW : 0;
-    constexpr bool in_ctx = layer == 0;                 // the input planes: sm.ctx (layer 0) or sm.h
-    constexpr bool planes = split_tail<trunk, layer>();  // the attention output as planes
-    static_assert(in_ctx || last, "a split in_proj after a split full layer: a pruned layer");
-    const float* bin = P + kOffs.o[layer_param(trunk, layer, INB)];
-    const int l = LANE(), i16 = l & 15, g = l >> 4, wv = TIDX() >> 6;
-    const _Float16* hp = reinterpret_cast<const _Float16*>(in_ctx ? sm.ctx : sm.h);
-    TailPre<trunk, layer, last, TR, 0, true> po;
-    [[maybe_unused]] f32x4 att0[last ? 1 : 3];  // chunk 0's attention output (in_ctx)
-    [[maybe_unused]] int ti0 = 0, d00 = 0;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {  // two chunks of 4 heads (LDS budget)
-        HPre<2> pq;
-        if (wv < 4) pq = hprefetch<2>(TID_C P, si, D, 64 * c + 16 * wv, 0);
-        {  // K (waves 0-3) / V (waves 4-7) of the chunk for all 80 tokens
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(bin + kv_row(wv, c) + 4 * g);
-            f32x4 hi[S], lo[S];
-            zero(hi);
-            zero(lo);
-            hgemm_tile<S, 2>(TID_C hi, lo, pkv, P, si, D, kv_row(wv, c), 0, hp, 0);
-            if constexpr (layer == 0) __asm__ volatile("" ::: "memory");  // the scales' LDS reads after the GEMM
-            const int col = (1 + (wv >> 2)) * 64 + 16 * (wv & 3) + 4 * g;
-#pragma unroll
-            for (int ct = 0; ct < S; ++ct)
-                *reinterpret_cast<f32x4*>(sm.big + (16 * ct + i16) * LDB + col) =
-                    (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, 16 * ct + i16) + bb;
-        }
-        if (wv < 4) {  // Q of the chunk for the query tokens (their SIMD partners did V)
-            const f32x4 bq = *reinterpret_cast<const f32x4*>(bin + 64 * c + 16 * wv + 4 * g);
-            f32x4 hi[CTQ], lo[CTQ];
-            zero(hi);
-            zero(lo);
-            hgemm_tile<CTQ, 2>(TID_C hi, lo, pq, P, si, D, 64 * c + 16 * wv, 0, hp, qtok0);
-            if constexpr (layer == 0) __asm__ volatile("" ::: "memory");
-#pragma unroll
-            for (int ct = 0; ct < CTQ; ++ct)
-                *reinterpret_cast<f32x4*>(sm.big + (qtok0 + 16 * ct + i16) * LDB + 16 * wv + 4 * g) =
-                    (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, qtok0 + 16 * ct + i16) + bq;
-        }
-        if (c == 0) pkv = hprefetch<2>(TID_C P, si, D, kv_row(wv, 1), 0);
-        else po = tail_prefetch<trunk, layer, last, TR, true>(TID_C P);
-        PTR(tb + 1 + 3 * c);
-        __syncthreads();
-        PTR(tb + 2 + 3 * c);
-        if constexpr (TR) store_qkv_chunk(TID_C sm, io.qkv, c, qtok0, b0);
-        if constexpr (!in_ctx) {
-            attention_chunk<planes, trunk, layer>(TID_C sm, c, S - 1, 1, P);
-        } else if constexpr (last) {  // one query position: threads < 256 own one task each
-            f32x4 o;
-            int ti = 0, d0 = 0;
-            if (TIDX() < 4 * SPW * 4) attention_task(TID_C sm, TIDX() >> 2, S - 1, o, ti, d0);
-            if (c == 0) {
-                att0[0] = o;
-                ti0 = ti;
-                d00 = d0;
-            } else if (TIDX() < 4 * SPW * 4) {
-                const float asc = attn_sc<planes, trunk, layer>(sm, ti & 15);
-                attention_out<planes>(TID_C sm, 0, ti0, d00, att0[0], asc);
-                attention_out<planes>(TID_C sm, 1, ti, d0, o, asc);
-            }
-        } else {
-            if (c == 0) {
-                attention_full_core(TID_C sm, 0, att0);
-            } else {
-                f32x4 o[3];
-                attention_full_core(TID_C sm, 1, o);
-                const float asc = attn_sc<planes, trunk, layer>(sm, (int)((TIDX() >> 4) & 15));
-                attention_full_store<planes>(TID_C sm, 0, att0, asc);
-                attention_full_store<planes>(TID_C sm, 1, o, asc);
-            }
-        }
-        __syncthreads();
-        PTR(tb + 3 + 3 * c);
-    }
-    layer_tail<trunk, layer, last, TR, F, 0, true>(TID_C sm, P, po, io, b0, pre_ln2);
-}
-
-// One post-LN nn.TransformerEncoderLayer (relu FFN 256, 8 heads). last: prune to column tile 4.
-// Work split: 8 waves, wave w and w+4 share a SIMD (and its MFMA pipe); every GEMM gives each
-// SIMD the same number of 16-row output tiles. `pkv` = the caller's prefetch of this layer's first
-// K/V weight blocks. Ends WITHOUT a final barrier: the caller prefetches its next weights, then syncs.
-template <int trunk, int layer, bool last, bool TR = false, class F = NoHook, bool SP = !TR>
-__device__ __forceinline__ void encoder_layer(TID_F Smem& sm, const float* __restrict__ P, KvPre<trunk, layer, TR, SP> pkv,
-                              const TrainLayerIO& io = TrainLayerIO{}, int b0 = 0, F pre_ln2 = F{}) {
-    if constexpr (split_kv<trunk, layer, TR, SP>()) {
-        encoder_layer_split<trunk, layer, last, TR, F>(TID_C sm, P, pkv, io, b0, pre_ln2);
-        return;
-    } else {
-    [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
-    PTR(tb);
-    const float* Win = P + kOffs.o[layer_param(trunk, layer, INW)];
-    const float* bin = P + kOffs.o[layer_param(trunk, layer, INB)];
-    const int wv = TIDX() >> 6;
-    constexpr int CTQ = last ? 1 : S;              // column tiles that need Q / out / LN / FFN
-    constexpr int DQ = depth<CTQ>();
-    constexpr int qtok0 = last ? (S - 1) * SPW : 0;
-    constexpr bool planes = SP && split_tail<trunk, layer>();
-
-    TailPre<trunk, layer, last, TR, 0, SP> po;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {  // two chunks of 4 heads (LDS budget)
-        APre<DQ> pq;
-        if (wv < 4) pq = prefetch<DQ>(TID_C Win, D, 64 * c + 16 * wv, 0);
-        // K (waves 0-3) / V (waves 4-7) of the chunk for all 80 tokens, one 16-row tile each
-        linear1<S, false, 2>(TID_C pkv, Win, D, bin, kv_row(wv, c), sm.h, LDH, 0, sm.big, LDB, (1 + (wv >> 2)) * 64 + 16 * (wv & 3), 0);
-        // Q of the chunk for the query tokens, waves 0-3 (their SIMD partners did V)
-        if (wv < 4) linear1<CTQ, false, DQ>(TID_C pq, Win, D, bin, 64 * c + 16 * wv, sm.h, LDH, qtok0, sm.big, LDB, 16 * wv, qtok0);
-        if (c == 0) pkv = prefetch<2>(TID_C Win, D, kv_row(wv, 1), 0);
-        else po = tail_prefetch<trunk, layer, last, TR, SP>(TID_C P);
-        PTR(tb + 1 + 3 * c);
-        __syncthreads();
-        PTR(tb + 2 + 3 * c);
-        if (TR && !kExpNoStore && !kExpNoQkvStream) {  // this chunk's Q (query tokens) / K / V -> qkv[row][part * 128 + 64 c + d]
-            // by waves 4-7 (V tiles: less MFMA work than the K + Q waves sharing their SIMDs)
-            for (int i = (int)TIDX() - NTHR / 2; i < TOK * 48; i += NTHR / 2) {
-                if (i < 0) break;
-                const int tok = i / 48, r = i - tok * 48, part = r >> 4, q = r & 15;
-                if (part == 0 && tok < qtok0) continue;
-                act_st(io.qkv + (size_t)trow(tok, b0) * 3 * D + part * D + 64 * c + 4 * q,
-                       *reinterpret_cast<const f32x4*>(sm.big + tok * LDB + part * 64 + 4 * q));
-            }
-        }
-        if (last) attention_chunk<planes, trunk, layer>(TID_C sm, c, S - 1, 1, P);
-        else attention_full<planes, trunk, layer>(TID_C sm, c, P);
-        __syncthreads();
-        PTR(tb + 3 + 3 * c);
-    }
-    layer_tail<trunk, layer, last, TR, F, 0, SP>(TID_C sm, P, po, io, b0, pre_ln2);
-    }
-}
-
-// Out-projection + LN1 + FFN + LN2 of an inference layer as split products (layer_tail's split
-// path): a full layer (80 tokens) or a pruned one (the 16 tokens of position 4). The attention
-// output's planes are in sm.ctx (attention_full / attention_chunk <true>); LN1 writes its output's
-// planes into sm.h and keeps the fp32 values in registers (LN2's residual); FFN1 writes the hidden
-// planes into big (features 0-127) and ctx (128-255); LN2 writes fp32 into sm.h -- or, when the next
-// layer's in_proj runs as split products, that layer's operand planes (and position 4 in fp32 to
-// sm.ctx rows 0-15). A pruned layer after such a layer takes its residual from sm.ctx rows 0-15.
-// Training mode (TR): the activations the backward reads are written as in layer_tail -- the
+// Out-projection + LN1 + FFN + LN2 of an encoder layer as split products, after the attention
+// output's planes are in sm.ctx (attention_full / attention_chunk): a full layer (80 tokens) or a
+// pruned one (the 16 tokens of position 4). `po` = the caller's prefetch of the first out_proj
+// weight blocks. LN1 writes its output's planes into sm.h and keeps the fp32 values in registers
+// (LN2's residual); FFN1 writes the hidden planes into big (features 0-127) and ctx (128-255); LN2
+// writes fp32 into sm.h -- or, when the next layer's in_proj runs as split products, that layer's
+// operand planes (and position 4 in fp32 to sm.ctx rows 0-15). A pruned layer after such a layer
+// takes its residual from sm.ctx rows 0-15.
+// Training mode (TR): the activations the backward reads are written to the workspace -- the
 // attention output and the FFN hidden from their planes (the values the GEMMs consumed), the
 // LayerNorm outputs from registers.
-// PSX (the K7 position-split forward): a full layer for the 16 tokens of one position, [qt, qt + 16),
-// its residual in sm.h, LN2's output as planes for the kernel's next in_proj (ps_inproj_split); and
-// K7's pruned layers take their residual from sm.h (PSX = 2).
+// PSX (the K7 position-split forward): a full layer for the 16 tokens of ONE window position,
+// [qt, qt + 16) (column tile qt / 16, [b * 5 + s] rows), its residual in sm.h, LN2's output as planes
+// for the kernel's next in_proj (ps_inproj); and K7's pruned layers take their residual from sm.h
+// (PSX = 2).
 template <int trunk, int layer, bool last, bool TR = false, class F = NoHook, int PSX = 0>
-__device__ __forceinline__ void layer_tail_split(TID_F Smem& sm, const float* __restrict__ P,
-                                                 const HPre<tail_depth<last, TR, PSX>()>& po,
-                                                 const TrainLayerIO& io = TrainLayerIO{}, int b0 = 0, F pre_ln2 = F{},
-                                                 int qt = 0) {
+__device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restrict__ P, const TailPre<last, TR, PSX>& po,
+                                           const TrainLayerIO& io = TrainLayerIO{}, int b0 = 0, F pre_ln2 = F{},
+                                           int qt = 0) {
     constexpr int DP = tail_depth<last, TR, PSX>();
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
     constexpr int CT = (last || PSX) ? 1 : S;
@@ -1400,113 +1165,150 @@ __device__ __forceinline__ void layer_tail_split(TID_F Smem& sm, const float* __
         TID_C sm, acc2, lp2, t0, LnOut{io.xhat2, PSX ? io.h2 : nullptr, io.rstd2, b0, last, !PSX}, nullptr, h1, ln2_sc);
     PTR(tb + 14);
 }
+// encoder_layer* call layer_tail through this forwarder; the K7 kernels call layer_tail itself. Not a
+// second concept: the extra call level only fixes the nesting in which the compiler inlines the tail.
+// Invariant: the code objects of k_policy_forward<false, ...> and k_rollout_steps depend on it -- with
+// the call made directly they hold the same instructions in another order and register numbering (a
+// few LayerNorm-partial address computations move). Fold it away only together with a same-box
+// benchmark of those kernels.
+template <int trunk, int layer, bool last, bool TR, class F = NoHook>
+__device__ __forceinline__ void layer_tail_fwd(TID_F Smem& sm, const float* __restrict__ P, const TailPre<last, TR>& po,
+                                               const TrainLayerIO& io, int b0, F pre_ln2 = F{}) {
+    layer_tail<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
+}
 
-// Out-projection + LN1 + FFN + LN2 of an encoder layer, after the attention output is in sm.ctx.
-// `po` = the caller's prefetch of the first out_proj weight blocks.
-template <int trunk, int layer, bool last, bool TR, class F, int PSX, bool SP>
-__device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restrict__ P, const TailPre<trunk, layer, last, TR, PSX, SP>& po,
-                           const TrainLayerIO& io, int b0, F pre_ln2, int qt) {
+// An encoder layer whose in_proj runs as split products: K / V of all 80 tokens and Q of the query
+// tokens from the fp16 planes of the layer input, fp32 Q | K | V into sm.big, then attention and
+// the layer tail. The input planes are
+//   layer >= 1: in sm.h (the previous layer's LN2 wrote them, and its position-4 rows in fp32 to
+//               sm.ctx rows 0-15: the residual of this pruned layer);
+//   layer 0 (training forward): in sm.ctx (the embedding wrote them beside its fp32 rows in sm.h) --
+//               so chunk 0's attention output waits in registers until chunk 1's GEMMs have read
+//               sm.ctx, then both chunks are written.
+template <int trunk, int layer, bool last, bool TR, class F = NoHook>
+__device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float* __restrict__ P, HPre<2> pkv,
+                                                    const TrainLayerIO& io, int b0, F pre_ln2) {
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
-    const float* Wo = P + kOffs.o[layer_param(trunk, layer, OUTW)];
-    const float* bo = P + kOffs.o[layer_param(trunk, layer, OUTB)];
-    const float* W1 = P + kOffs.o[layer_param(trunk, layer, L1W)];
-    const float* b1 = P + kOffs.o[layer_param(trunk, layer, L1B)];
-    const float* W2 = P + kOffs.o[layer_param(trunk, layer, L2W)];
-    const float* b2 = P + kOffs.o[layer_param(trunk, layer, L2B)];
-    const int wv = TIDX() >> 6;
-    constexpr int CTQ = (last || PSX) ? 1 : S;
-    constexpr int DQ = depth<CTQ>();
-    const int qtok0 = last ? (S - 1) * SPW : (PSX ? qt : 0);
-    const int qtok1 = qtok0 + SPW * CTQ;
-    if (TR) store_rows(TID_C sm.ctx, LDH, io.o, D, 0, D, qtok0, b0, last, qtok1, !PSX);  // attention output
-    // out projection, h = LN1(h + attn) in its epilogue
-    APre<DQ> pf1a, pf1b;
-    // inference, full layer (the critic's layer 0): the FFN runs as split products on the f16
-    // matrix cores (hgemm_tile): LN1 writes its output as the two fp16 planes into sm.h and keeps
-    // the fp32 values in registers (LN2's residual), FFN1 writes the hidden planes into big
-    // (features 0-127) and ctx (128-255), FFN2 reads them
-    if constexpr (SP && !PSX && split_tail<trunk, layer>()) {
-        layer_tail_split<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
-        return;
-    } else {
-    // a pruned layer after a split full layer: the residual (its input at position 4) is in sm.ctx
-    // rows 0-15 (sm.h holds the input's fp16 planes)
-    constexpr bool kResCtx = SP && last && !PSX && split_inproj<trunk, layer>();
-    // inference, full layer: the wave's own 16 LayerNorm output features are FFN1's k-block wv, so
-    // its MFMAs over that block run from registers before the barrier (beside the other waves'
-    // LayerNorm work) and the GEMM after it covers the other 7 blocks (k-block order rotated)
-    constexpr bool kRot = !TR && CTQ == S;
-    [[maybe_unused]] APre<1> own_a, own_b;
-    [[maybe_unused]] f32x4 fa[CTQ], fb[CTQ];
-    {
-        const f32x4 bo4 = ln_bias(TID_C bo);
-        f32x4 acc[CTQ];
-        zero(acc);
-        gemm_tile<CTQ, DQ>(TID_C acc, po, Wo, D, 16 * wv, 0, sm.ctx, LDH, qtok0);
-        PTR(tb + 7);
-        const LnPar lp = ln_load(TID_C bo4, P + kOffs.o[layer_param(trunk, layer, N1W)], P + kOffs.o[layer_param(trunk, layer, N1B)]);
-        if constexpr (kRot) {
-            own_a = prefetch_rot<1>(TID_C W1, D, 16 * wv, wv);
-            own_b = prefetch_rot<1>(TID_C W1, D, 128 + 16 * wv, wv);
-            pf1a = prefetch_rot<DQ>(TID_C W1, D, 16 * wv, wv + 1);
-            pf1b = prefetch_rot<DQ>(TID_C W1, D, 128 + 16 * wv, wv + 1);
-            f32x4 outv[CTQ];
-            residual_layernorm<CTQ, TR>(TID_C sm, acc, lp, qtok0, LnOut{io.xhat1, PSX ? io.h1 : nullptr, io.rstd1, b0, last, !PSX}, outv);
-            zero(fa);
-            zero(fb);
+    PTR(tb);
+    constexpr int si = split_slot(layer_param(trunk, layer, INW));
+    constexpr int CTQ = last ? 1 : S, qtok0 = last ? (S - 1) * SPW : 0;
+    constexpr bool in_ctx = layer == 0;                 // the input planes: sm.ctx (layer 0) or sm.h
+    static_assert(in_ctx || last, "a split in_proj after a full layer: a pruned layer");
+    const float* bin = P + kOffs.o[layer_param(trunk, layer, INB)];
+    const int l = LANE(), i16 = l & 15, g = l >> 4, wv = TIDX() >> 6;
+    const _Float16* hp = reinterpret_cast<const _Float16*>(in_ctx ? sm.ctx : sm.h);
+    TailPre<last, TR> po;
+    [[maybe_unused]] f32x4 att0[last ? 1 : 3];  // chunk 0's attention output (in_ctx)
+    [[maybe_unused]] int ti0 = 0, d00 = 0;
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+    for (int c = 0; c < 2; ++c) {  // two chunks of 4 heads (LDS budget)
+        HPre<2> pq;
+        if (wv < 4) pq = hprefetch<2>(TID_C P, si, D, 64 * c + 16 * wv, 0);
+        {  // K (waves 0-3) / V (waves 4-7) of the chunk for all 80 tokens
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(bin + kv_row(wv, c) + 4 * g);
+            f32x4 hi[S], lo[S];
+            zero(hi);
+            zero(lo);
+            hgemm_tile<S, 2>(TID_C hi, lo, pkv, P, si, D, kv_row(wv, c), 0, hp, 0);
+            if constexpr (layer == 0) __asm__ volatile("" ::: "memory");  // the scales' LDS reads after the GEMM
+            const int col = (1 + (wv >> 2)) * 64 + 16 * (wv & 3) + 4 * g;
 #pragma unroll
-                for (int ct = 0; ct < CTQ; ++ct) {
-                    fa[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(own_a.a[0][j], outv[ct][j], fa[ct], 0, 0, 0);
-                    fb[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(own_b.a[0][j], outv[ct][j], fb[ct], 0, 0, 0);
-                }
+            for (int ct = 0; ct < S; ++ct)
+                *reinterpret_cast<f32x4*>(sm.big + (16 * ct + i16) * LDB + col) =
+                    (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, 16 * ct + i16) + bb;
+        }
+        if (wv < 4) {  // Q of the chunk for the query tokens (their SIMD partners did V)
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(bin + 64 * c + 16 * wv + 4 * g);
+            f32x4 hi[CTQ], lo[CTQ];
+            zero(hi);
+            zero(lo);
+            hgemm_tile<CTQ, 2>(TID_C hi, lo, pq, P, si, D, 64 * c + 16 * wv, 0, hp, qtok0);
+            if constexpr (layer == 0) __asm__ volatile("" ::: "memory");
+#pragma unroll
+            for (int ct = 0; ct < CTQ; ++ct)
+                *reinterpret_cast<f32x4*>(sm.big + (qtok0 + 16 * ct + i16) * LDB + 16 * wv + 4 * g) =
+                    (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, qtok0 + 16 * ct + i16) + bq;
+        }
+        if (c == 0) pkv = hprefetch<2>(TID_C P, si, D, kv_row(wv, 1), 0);
+        else po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
+        PTR(tb + 1 + 3 * c);
+        __syncthreads();
+        PTR(tb + 2 + 3 * c);
+        if constexpr (TR) store_qkv_chunk(TID_C sm, io.qkv, c, qtok0, b0);
+        if constexpr (!in_ctx) {
+            attention_chunk<trunk, layer>(TID_C sm, c, S - 1, 1, P);
+        } else if constexpr (last) {  // one query position: threads < 256 own one task each
+            f32x4 o;
+            int ti = 0, d0 = 0;
+            if (TIDX() < 4 * SPW * 4) attention_task(TID_C sm, TIDX() >> 2, S - 1, o, ti, d0);
+            if (c == 0) {
+                att0[0] = o;
+                ti0 = ti;
+                d00 = d0;
+            } else if (TIDX() < 4 * SPW * 4) {
+                const float asc = att_sc<trunk, layer>(sm, ti & 15).sc;
+                attention_out(TID_C sm, 0, ti0, d00, att0[0], asc);
+                attention_out(TID_C sm, 1, ti, d0, o, asc);
+            }
         } else {
-            pf1a = prefetch<DQ>(TID_C W1, D, 16 * wv, 0);
-            pf1b = prefetch<DQ>(TID_C W1, D, 128 + 16 * wv, 0);
-            if constexpr (kResCtx) {
-                const f32x4 r4[1] = {*reinterpret_cast<const f32x4*>(sm.ctx + (LANE() & 15) * LDH + 16 * wv + 4 * (LANE() >> 4))};
-                residual_layernorm<CTQ, TR>(TID_C sm, acc, lp, qtok0, LnOut{}, nullptr, r4);
+            if (c == 0) {
+                attention_full_core(TID_C sm, 0, att0);
             } else {
-                residual_layernorm<CTQ, TR>(TID_C sm, acc, lp, qtok0, LnOut{io.xhat1, PSX ? io.h1 : nullptr, io.rstd1, b0, last, !PSX});
+                f32x4 o[3];
+                attention_full_core(TID_C sm, 1, o);
+                const float asc = att_sc<trunk, layer>(sm, (int)((TIDX() >> 4) & 15)).sc;
+                attention_full_store(TID_C sm, 0, att0, asc);
+                attention_full_store(TID_C sm, 1, o, asc);
             }
         }
+        __syncthreads();
+        PTR(tb + 3 + 3 * c);
     }
-    PTR(tb + 8);
-    __syncthreads();
-    PTR(tb + 9);
-    // FFN: hidden features 0-127 -> big, 128-255 -> ctx (both free now), then one K=256 GEMM
-    if constexpr (kRot) {
-        const int grow = 4 * (LANE() >> 4);
-        const f32x4 ba = *reinterpret_cast<const f32x4*>(b1 + 16 * wv + grow);
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(b1 + 128 + 16 * wv + grow);
-        gemm_tile_rot<CTQ, DQ>(TID_C fa, pf1a, W1, D, 16 * wv, sm.h, LDH, qtok0, wv + 1);
-        store_tile<CTQ, true>(TID_C fa, ba, sm.big, LDF, 16 * wv, qtok0);
-        gemm_tile_rot<CTQ, DQ>(TID_C fb, pf1b, W1, D, 128 + 16 * wv, sm.h, LDH, qtok0, wv + 1);
-        store_tile<CTQ, true>(TID_C fb, bb, sm.ctx, LDF, 16 * wv, qtok0);
+    layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
+}
+
+// One post-LN nn.TransformerEncoderLayer (relu FFN 256, 8 heads). last: prune to column tile 4.
+// Work split: 8 waves, wave w and w+4 share a SIMD (and its MFMA pipe); every GEMM gives each
+// SIMD the same number of 16-row output tiles. `pkv` = the caller's prefetch of this layer's first
+// K/V weight blocks. Ends WITHOUT a final barrier: the caller prefetches its next weights, then syncs.
+template <int trunk, int layer, bool last, bool TR = false, class F = NoHook>
+__device__ __forceinline__ void encoder_layer(TID_F Smem& sm, const float* __restrict__ P, KvPre<trunk, layer, TR> pkv,
+                              const TrainLayerIO& io = TrainLayerIO{}, int b0 = 0, F pre_ln2 = F{}) {
+    if constexpr (split_kv<trunk, layer, TR>()) {
+        encoder_layer_split<trunk, layer, last, TR, F>(TID_C sm, P, pkv, io, b0, pre_ln2);
+        return;
     } else {
-        linear1<CTQ, true, DQ>(TID_C pf1a, W1, D, b1, 16 * wv, sm.h, LDH, qtok0, sm.big, LDF, 16 * wv, qtok0);
-        linear1<CTQ, true, DQ>(TID_C pf1b, W1, D, b1, 128 + 16 * wv, sm.h, LDH, qtok0, sm.ctx, LDF, 16 * wv, qtok0);
+    // layer 0 of the inference forward: its in_proj on the f32 MFMA from the embedding's fp32 rows
+    static_assert(!TR, "the training forward's in_proj GEMMs are split products");
+    [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
+    PTR(tb);
+    const float* Win = P + kOffs.o[layer_param(trunk, layer, INW)];
+    const float* bin = P + kOffs.o[layer_param(trunk, layer, INB)];
+    const int wv = TIDX() >> 6;
+    constexpr int CTQ = last ? 1 : S;              // column tiles that need Q / out / LN / FFN
+    constexpr int DQ = depth<CTQ>();
+    constexpr int qtok0 = last ? (S - 1) * SPW : 0;
+
+    TailPre<last, TR> po;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {  // two chunks of 4 heads (LDS budget)
+        APre<DQ> pq;
+        if (wv < 4) pq = prefetch<DQ>(TID_C Win, D, 64 * c + 16 * wv, 0);
+        // K (waves 0-3) / V (waves 4-7) of the chunk for all 80 tokens, one 16-row tile each
+        linear1<S, false, 2>(TID_C pkv, Win, D, bin, kv_row(wv, c), sm.h, LDH, 0, sm.big, LDB, (1 + (wv >> 2)) * 64 + 16 * (wv & 3), 0);
+        // Q of the chunk for the query tokens, waves 0-3 (their SIMD partners did V)
+        if (wv < 4) linear1<CTQ, false, DQ>(TID_C pq, Win, D, bin, 64 * c + 16 * wv, sm.h, LDH, qtok0, sm.big, LDB, 16 * wv, qtok0);
+        if (c == 0) pkv = prefetch<2>(TID_C Win, D, kv_row(wv, 1), 0);
+        else po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
+        PTR(tb + 1 + 3 * c);
+        __syncthreads();
+        PTR(tb + 2 + 3 * c);
+        if (last) attention_chunk<trunk, layer>(TID_C sm, c, S - 1, 1, P);
+        else attention_full<trunk, layer>(TID_C sm, c, P);
+        __syncthreads();
+        PTR(tb + 3 + 3 * c);
     }
-    const APre<DQ> pf2a = prefetch<DQ>(TID_C W2, FF, 16 * wv, 0);
-    PTR(tb + 10);
-    __syncthreads();
-    PTR(tb + 11);
-    const APre<DQ> pf2b = prefetch<DQ>(TID_C W2, FF, 16 * wv, 128);
-    if (TR) {  // FFN hidden (post-ReLU): features 0-127 in big, 128-255 in ctx
-        store_rows(TID_C sm.big, LDF, io.u, FF, 0, D, qtok0, b0, last, qtok1, !PSX);
-        store_rows(TID_C sm.ctx, LDF, io.u, FF, D, D, qtok0, b0, last, qtok1, !PSX);
-    }
-    const f32x4 b24 = ln_bias(TID_C b2);
-    f32x4 acc2[CTQ];
-    zero(acc2);
-    gemm_tile<CTQ, DQ>(TID_C acc2, pf2a, W2, FF, 16 * wv, 0, sm.big, LDF, qtok0);
-    gemm_tile<CTQ, DQ>(TID_C acc2, pf2b, W2, FF, 16 * wv, 128, sm.ctx, LDF, qtok0);
-    PTR(tb + 12);
-    const LnPar lp2 = ln_load(TID_C b24, P + kOffs.o[layer_param(trunk, layer, N2W)], P + kOffs.o[layer_param(trunk, layer, N2B)]);
-    pre_ln2();
-    residual_layernorm<CTQ, TR>(TID_C sm, acc2, lp2, qtok0, LnOut{io.xhat2, PSX ? io.h2 : nullptr, io.rstd2, b0, last, !PSX});
-    PTR(tb + 14);
+    layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
     }
 }
 
@@ -1693,7 +1495,6 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
                                    const RowIO& rio, int b0) {
     constexpr bool last = trunk == kActorTrunk;  // the actor's layer 0 is its last (pruned) layer
     constexpr int P0 = 3 - NP, ROFF = trunk == kActorTrunk ? 0 : 2 * D;
-    constexpr bool planes = split_tail<trunk, 0>();  // attention output as split-product planes
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1);
     PTR(tb);
     const float* Win = P + kOffs.o[layer_param(trunk, 0, INW)];
@@ -1725,7 +1526,7 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
     PTR(tb + 13);
     const float* pl = reinterpret_cast<const float*>(sm.red);
     const int q = TIDX() & 15;
-    TailPre<trunk, 0, last, false> po;
+    TailPre<last, false> po;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         // Q | K | V of the chunk -> sm.big: positions 0-3 from the ring, position 4 from acc
@@ -1750,12 +1551,12 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
         __syncthreads();
         PTR(tb + 2 + 3 * c);
         if (c == 0) ppos_stage(TID_C sm, rp, 1);  // sm.red is read again only by the chunk-1 assembly
-        if (last) attention_chunk<planes, trunk, 0>(TID_C sm, c, S - 1, 1, P);
-        else attention_full<planes, trunk, 0>(TID_C sm, c, P);
+        if (last) attention_chunk<trunk, 0>(TID_C sm, c, S - 1, 1, P);
+        else attention_full<trunk, 0>(TID_C sm, c, P);
         __syncthreads();
         PTR(tb + 3 + 3 * c);
     }
-    layer_tail<trunk, 0, last, false>(TID_C sm, P, po, TrainLayerIO{}, b0);
+    layer_tail_fwd<trunk, 0, last, false>(TID_C sm, P, po, TrainLayerIO{}, b0);
 }
 
 // Everything layer 0 of a trunk needs before its new-row GEMM (which then issues the ring loads
@@ -2068,15 +1869,15 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
     // training mode: the first trunk's embedding operands and first K/V weight blocks are loaded
     // before the minibatch gather stores its rows (a load behind a store burst waits for the burst)
     [[maybe_unused]] EmbPre ep_a, ep_c;
-    [[maybe_unused]] KvPre<kActorTrunk, 0, TR, kTrainSplit> pkv_a;
-    [[maybe_unused]] KvPre<kCriticTrunk, 0, TR, kTrainSplit> pkv_c;
+    [[maybe_unused]] KvPre<kActorTrunk, 0, TR> pkv_a;
+    [[maybe_unused]] KvPre<kCriticTrunk, 0, TR> pkv_c;
     if constexpr (TR) {
         if (do_actor && !critic_first) {
             ep_a = embed_load<kActorTrunk>(TID_C P);
-            pkv_a = kv_prefetch<kActorTrunk, 0, TR, kTrainSplit>(TID_C P);
+            pkv_a = kv_prefetch<kActorTrunk, 0, TR>(TID_C P);
         } else {
             ep_c = embed_load<kCriticTrunk>(TID_C P);
-            pkv_c = kv_prefetch<kCriticTrunk, 0, TR, kTrainSplit>(TID_C P);
+            pkv_c = kv_prefetch<kCriticTrunk, 0, TR>(TID_C P);
         }
     }
     gather_windows<TR, ROWS>(TID_C sm, states, B, io, b0, do_actor, P + kRangeOff);
@@ -2129,7 +1930,7 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
     [[maybe_unused]] auto actor = [&] {
         if constexpr (TR && !ROWS) {
             // the split layer-0 in_proj reads the embedding's planes in sm.ctx
-            embed_apply<kActorTrunk, TR, kEmbH, split_kv<kActorTrunk, 0, TR, kTrainSplit>()>(TID_C sm, ep_a, io.e[0],
+            embed_apply<kActorTrunk, TR, kEmbH, split_kv<kActorTrunk, 0, TR>()>(TID_C sm, ep_a, io.e[0],
                                                                                            nullptr, b0);
             PTR(2);
             __syncthreads();
@@ -2137,10 +1938,10 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
                 if (wv < 4) ph = prefetch<kHd>(TID_C headw_a, D, 16 * wv, 0);
                 if (do_critic && !critic_first) {
                     ep_c = embed_load<kCriticTrunk>(TID_C P);
-                    pkv_c = kv_prefetch<kCriticTrunk, 0, TR, kTrainSplit>(TID_C P);
+                    pkv_c = kv_prefetch<kCriticTrunk, 0, TR>(TID_C P);
                 }
             };
-            encoder_layer<kActorTrunk, 0, true, TR, decltype(hook), kTrainSplit>(TID_C sm, P, pkv_a, io.L[0], b0, hook);
+            encoder_layer<kActorTrunk, 0, true, TR, decltype(hook)>(TID_C sm, P, pkv_a, io.L[0], b0, hook);
             __syncthreads();
             PTR(3);
             head_mlp<kActorHead, 2, kHd>(TID_C sm, P, ph, sm.logits);
@@ -2177,14 +1978,14 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             __syncthreads();
             encoder_layer_rows<kCriticTrunk>(TID_C sm, P, pw, rp, rio, b0);
         }
-        KvPre<kCriticTrunk, 1, TR, TR ? kTrainSplit : true> pkv;
+        KvPre<kCriticTrunk, 1, TR> pkv;
         if constexpr (!ROWS) {
             if constexpr (TR) {
-                embed_apply<kCriticTrunk, TR, kEmbH, split_kv<kCriticTrunk, 0, TR, kTrainSplit>()>(TID_C sm, ep_c, io.e[1],
+                embed_apply<kCriticTrunk, TR, kEmbH, split_kv<kCriticTrunk, 0, TR>()>(TID_C sm, ep_c, io.e[1],
                                                                                                  nullptr, b0);
                 __syncthreads();
-                auto hook = [&] { pkv = kv_prefetch<kCriticTrunk, 1, TR, kTrainSplit>(TID_C P); };
-                encoder_layer<kCriticTrunk, 0, false, TR, decltype(hook), kTrainSplit>(TID_C sm, P, pkv_c, io.L[1], b0, hook);
+                auto hook = [&] { pkv = kv_prefetch<kCriticTrunk, 1, TR>(TID_C P); };
+                encoder_layer<kCriticTrunk, 0, false, TR, decltype(hook)>(TID_C sm, P, pkv_c, io.L[1], b0, hook);
             } else {
                 APre<2> pkv0 = prefetch<2>(TID_C P + kOffs.o[layer_param(kCriticTrunk, 0, INW)], D, kv_row(wv, 0), 0);
                 embed<kCriticTrunk, TR>(TID_C sm, P, io.e[1], nullptr, b0);
@@ -2198,7 +1999,7 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             auto hook = [&] {
                 if (wv < 4) ph = prefetch<kHd>(TID_C headw_c, D, 16 * wv, 0);
             };
-            encoder_layer<kCriticTrunk, 1, true, TR, decltype(hook), kTrainSplit>(TID_C sm, P, pkv, io.L[2], b0, hook);
+            encoder_layer<kCriticTrunk, 1, true, TR, decltype(hook)>(TID_C sm, P, pkv, io.L[2], b0, hook);
         } else {
             encoder_layer<kCriticTrunk, 1, true, TR>(TID_C sm, P, pkv, io.L[2], b0);
         }
@@ -2219,7 +2020,7 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
     if constexpr (TR) {
         if (critic_first) {  // the actor's operands now (not prefetched: the critic's hooks are full)
             ep_a = embed_load<kActorTrunk>(TID_C P);
-            pkv_a = kv_prefetch<kActorTrunk, 0, TR, kTrainSplit>(TID_C P);
+            pkv_a = kv_prefetch<kActorTrunk, 0, TR>(TID_C P);
             __syncthreads();  // the actor's trunk reuses the critic's buffers (sm.z after store_hidden)
             actor();
         }
@@ -2601,8 +2402,7 @@ __device__ __forceinline__ void ln_bwd_load(LnBwdPre& a, const float* __restrict
         }
     }
 }
-// PL: dst receives the two fp16 planes of the split products (the next GEMM's operand) instead of fp32.
-template <bool PL = false>
+// dst receives the two fp16 planes of the split products (the next GEMM's operand).
 __device__ void ln_bwd_lds(const float* src, float* dst, const LnBwdPre& a, float* __restrict__ gout,
                            float* __restrict__ part, float* __restrict__ bias, int t0, int b0, bool compact,
                            float* scratch, int t1 = TOK) {
@@ -2624,13 +2424,8 @@ __device__ void ln_bwd_lds(const float* src, float* dst, const LnBwdPre& a, floa
         const float m1 = row16_sum(hsum(gw0) + hsum(gw1)) * (1.0f / D);
         const float m2 = row16_sum(hsum(gw0 * x0) + hsum(gw1 * x1)) * (1.0f / D);
         const f32x4 d0 = rs * (gw0 - m1 - x0 * m2), d1 = rs * (gw1 - m1 - x1 * m2);
-        if constexpr (PL) {
-            hsplit_store(reinterpret_cast<_Float16*>(dst), psw(tok, f0), d0);
-            hsplit_store(reinterpret_cast<_Float16*>(dst), psw(tok, f0 + 4), d1);
-        } else {
-            st4(dst + tok * LDH + f0, d0);
-            st4(dst + tok * LDH + f0 + 4, d1);
-        }
+        hsplit_store(reinterpret_cast<_Float16*>(dst), psw(tok, f0), d0);
+        hsplit_store(reinterpret_cast<_Float16*>(dst), psw(tok, f0 + 4), d1);
         dy_st4(gout + r * D + f0, d0);
         dy_st4(gout + r * D + f0 + 4, d1);
         pw0 += g0 * x0; pw1 += g1 * x1;
@@ -2657,10 +2452,9 @@ __device__ void ln_bwd_lds(const float* src, float* dst, const LnBwdPre& a, floa
 //   dv_j = sum_i P_ij g_i; dP_ij = g_i . v_j; dS_ij = P_ij (dP_ij - sum_k P_ik dP_ik);
 //   dq_i = sum_j dS_ij k_j / 4; dk_j = sum_i dS_ij q_i / 4.
 // One (sample, head) task per 8 lanes, 2 of the 16 head dims each (all 512 threads; dot products
-// reduced over the 8 lanes with two quad permutes and a half-row mirror). dq | dk | dv ->
-// sm.big [tok][3 x 64] (the forward's chunk layout; pruned layers: dq zero outside the token-4
-// query rows); the caller copies them to the dqkv rows. Per-wave sums over the wave's 2 samples of
-// dq, dk, dv -> scratch [wave][192] (in_proj bias partials).
+// reduced over the 8 lanes with two quad permutes and a half-row mirror). dq | dk | dv -> sm.big
+// as fp16 planes and the dqkv rows (attn_out2; dq on the query rows only). Per-wave sums over the
+// wave's 2 samples of dq, dk, dv -> scratch [wave][192] (in_proj bias partials).
 __device__ __forceinline__ float add_hmirror8(float v) {  // + lane 7 - i within each group of 8
     return v + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));
 }
@@ -2697,32 +2491,27 @@ __device__ __forceinline__ void attn_bwd_load(AttnPre& a, const float* __restric
     for (int i = 0; i < S; ++i)
         if (qsel >= 0 ? i == qsel : (!last || i == S - 1)) a.q[i] = ld2_once(qkv + (rb + i) * 3 * D + col);
 }
-// SP (split-product backward): dq | dk | dv go to sm.big as the two fp16 planes of the W_in^T GEMM's
-// operand -- both planes of a token in one row, [tok][plane 1: 192 halves | plane 2: 192 | pad 16]
-// (800-B rows: token i16 at bank offset 8 i16, conflict-free ds_read_b128 operand reads) -- and,
-// exact, straight to the dqkv rows (dqkv != nullptr).
+// dq | dk | dv go to sm.big as the two fp16 planes of the W_in^T GEMM's operand -- both planes of a
+// token in one row, [tok][plane 1: 192 halves | plane 2: 192 | pad 16] (800-B rows: token i16 at
+// bank offset 8 i16, conflict-free ds_read_b128 operand reads) -- and, exact, straight to the dqkv
+// rows (position split: dk / dv to kvc instead).
 constexpr int kLdbP = 2 * LDB, kPlaneB = 3 * 64;  // halves per row, plane 2 within the row
 static_assert(kPlaneB + 3 * 64 <= kLdbP, "both planes in an LDB row");
 __device__ __forceinline__ void attn_out2(Smem& sm, float* __restrict__ dqkv, int b0, int tok, int col, int part,
-                                          int c, f32x2 v, bool sp, float* __restrict__ kvc = nullptr, int kblk = 0) {
-    if (sp) {
-        _Float16* bp = reinterpret_cast<_Float16*>(sm.big) + tok * kLdbP + part * 64 + col;
-        const _Float16 a0 = (_Float16)v.x, a1 = (_Float16)v.y;
-        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<f16x2*>(bp) = f16x2{a0, a1};
-        *reinterpret_cast<f16x2*>(bp + kPlaneB) = f16x2{f16_lo(v.x, a0), f16_lo(v.y, a1)};
-        if (kvc && part > 0)  // position split: this query position's share of every position's dk / dv
-            st2(kvc + ((size_t)kblk * TOK + tok) * 2 * D + (part - 1) * D + 64 * c + col, v);
-        else
-            dy_st2(dqkv + (size_t)trow(tok, b0) * 3 * D + part * D + 64 * c + col, v);
-    } else {
-        st2(sm.big + tok * LDB + part * 64 + col, v);
-    }
+                                          int c, f32x2 v, float* __restrict__ kvc = nullptr, int kblk = 0) {
+    _Float16* bp = reinterpret_cast<_Float16*>(sm.big) + tok * kLdbP + part * 64 + col;
+    const _Float16 a0 = (_Float16)v.x, a1 = (_Float16)v.y;
+    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<f16x2*>(bp) = f16x2{a0, a1};
+    *reinterpret_cast<f16x2*>(bp + kPlaneB) = f16x2{f16_lo(v.x, a0), f16_lo(v.y, a1)};
+    if (kvc && part > 0)  // position split: this query position's share of every position's dk / dv
+        st2(kvc + ((size_t)kblk * TOK + tok) * 2 * D + (part - 1) * D + 64 * c + col, v);
+    else
+        dy_st2(dqkv + (size_t)trow(tok, b0) * 3 * D + part * D + 64 * c + col, v);
 }
-template <bool last, bool SP = false>
-__device__ void attn_bwd_chunk(Smem& sm, const AttnPre& a, int c, float* scratch, int qsel = -1,
-                               float* __restrict__ dqkv = nullptr, int b0 = 0, float* __restrict__ kvc = nullptr,
-                               int kblk = 0) {
+template <bool last>
+__device__ void attn_bwd_chunk(Smem& sm, const AttnPre& a, int c, float* scratch, int qsel, float* __restrict__ dqkv,
+                               int b0, float* __restrict__ kvc, int kblk) {
     const int o8 = tid_x() & 7, hh = (tid_x() >> 3) & 3, p = tid_x() >> 5;
     const int d0 = hh * HD + 2 * o8;
     const int col = 64 * c + d0;
@@ -2779,13 +2568,13 @@ __device__ void attn_bwd_chunk(Smem& sm, const AttnPre& a, int c, float* scratch
             if (kQ4) dq *= 0.25f;
             sdq += dq;
         }
-        if (!SP || (qsel >= 0 ? i == qsel : (!last || i == S - 1))) attn_out2(sm, dqkv, b0, i * SPW + p, d0, 0, c, dq, SP);
+        if (qsel >= 0 ? i == qsel : (!last || i == S - 1)) attn_out2(sm, dqkv, b0, i * SPW + p, d0, 0, c, dq);
     }
     f32x2 sk = {0.f, 0.f}, sv = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < S; ++j) {
-        attn_out2(sm, dqkv, b0, j * SPW + p, d0, 1, c, dk[j], SP, kvc, kblk);
-        attn_out2(sm, dqkv, b0, j * SPW + p, d0, 2, c, dv[j], SP, kvc, kblk);
+        attn_out2(sm, dqkv, b0, j * SPW + p, d0, 1, c, dk[j], kvc, kblk);
+        attn_out2(sm, dqkv, b0, j * SPW + p, d0, 2, c, dv[j], kvc, kblk);
         sk += dk[j];
         sv += dv[j];
     }
@@ -2804,8 +2593,6 @@ __device__ void attn_bwd_chunk(Smem& sm, const AttnPre& a, int c, float* scratch
     }
 }
 
-// Backward of one post-LN encoder layer. On entry sm.h holds dL/d(layer output) for the tokens
-// >= qtok0; on exit sm.h holds dL/d(layer input) for all 80 tokens. Ends with a barrier.
 // The embedding backward's global inputs (embed_bwd): this thread's 20 embedding values (the ReLU
 // mask) and one float4 of the input windows, loaded by the layer-0 backward right after its last
 // GEMM (every weight load of the layer issued: nothing waits behind them), so their latency hides
@@ -2824,21 +2611,29 @@ __device__ __forceinline__ void embed_bwd_load(EmbBwdPre& ep, const float* __res
                               : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-enum { kBwdFull = 0, kBwdNoDx = 1, kBwdPos = 2 };  // bwd_layer's MODE (see bwd_layer)
-constexpr bool kBwdSplit = true;  // K6 (k_policy_backward) on split products
-constexpr bool kPsSplit = true;   // the K7 position-split kernels (k_ps_f1..f3, k_ps_b1..b3) on split products
-static_assert(kTrainF32LayerCopies || (kTrainSplit && kBwdSplit && kPsSplit),
-              "a training kernel on f32 products reads the fp32 layer copies policy_pack_train leaves NaN");
-// The layer backward as split products (bwd_layer<..., SP>): the same phases, barriers and outputs
-// as the f32 path below, for every MODE.
+enum { kBwdFull = 0, kBwdNoDx = 1, kBwdPos = 2 };  // bwd_layer's MODE
+// Backward of one post-LN encoder layer. On entry sm.h holds dL/d(layer output) for the tokens
+// >= qtok0; on exit (kBwdFull) sm.h holds dL/d(layer input) for all 80 tokens. Ends with a barrier.
+// Every dX GEMM runs as split products on the f16 MFMA -- A = the transposed split copies (PT is
+// this layer's packedT, the caller's offset: its split copy at PT + kTSplit), B = planes the
+// producing epilogue writes: df (LN2 backward -> sm.ctx), du (-> sm.big / sm.h), dz1 (LN1 backward
+// -> sm.h), dq | dk | dv (attention backward -> sm.big, rows of kLdbP halves, attn_out2); the
+// residual terms read back from planes are x1 + 2^-11 x2.
+// ln2_pre: this layer's LN2-backward operands, already loaded by the caller (nullptr: load here);
+// next_load: issues the next phase's global loads behind this layer's last weight loads.
+// MODE (the position-split training step, K7 below): kBwdFull = the whole layer; kBwdNoDx = stop after
+// the attention backward (dqkv rows and bias partials written; no W_in^T GEMM, no residual -- the
+// per-position kernels form dL/d(layer input)); kBwdPos = a full layer for the 16 query tokens of
+// ONE window position (tokens [qt, qt + 16), [b * 5 + s] rows, partial row prow): its dq rows go to
+// dqkv, its contributions to every position's dk / dv to kvc ([prow][80 tokens][dk 128 | dv 128]).
 template <int trunk, int layer, bool last, int TB, class F, int MODE>
-__device__ void bwd_layer_split(Smem& sm, const float* __restrict__ P, const float* __restrict__ PT, const BwdLayerIO& io,
-                                int b0, EmbBwdPre* ep, const float* e_emb, const float* xg, const LnBwdPre* ln2_pre,
-                                F next_load, int liT, int qt, int prow, float* __restrict__ kvc) {
+__device__ void bwd_layer(Smem& sm, const float* __restrict__ P, const float* __restrict__ PT, const BwdLayerIO& io,
+                          int b0, EmbBwdPre* ep, const float* e_emb, const float* xg, const LnBwdPre* ln2_pre,
+                          F next_load, int qt, int prow, float* __restrict__ kvc) {
+    static_assert(MODE != kBwdPos || !last, "position split: full layers only");
     constexpr int CTQ = (last || MODE == kBwdPos) ? 1 : S;
     const int qtok0 = last ? (S - 1) * SPW : (MODE == kBwdPos ? qt : 0), qtok1 = qtok0 + SPW * CTQ;
     const int qsel = MODE == kBwdPos ? qt / SPW : -1;
-    (void)liT;  // PT is this layer's packedT (the caller's offset): its split copy at PT + kTSplit
     const int sWin = kTSplit + kTWin, sWo = kTSplit + kTWo, sW1 = kTSplit + kTW1, sW2 = kTSplit + kTW2;
     const int wv = tid_x() >> 6, l = lane_id(), i16 = l & 15, g = l >> 4;
     const int fo = 16 * wv + 4 * g;
@@ -2859,8 +2654,8 @@ __device__ void bwd_layer_split(Smem& sm, const float* __restrict__ P, const flo
     LnBwdPre lnp;
     if (ln2_pre) lnp = *ln2_pre;
     else ln_bwd_load(lnp, io.xhat2, io.rstd2, P + kOffs.o[layer_param(trunk, layer, N2W)], qtok0, b0, last, qtok1);
-    ln_bwd_lds<true>(sm.h, sm.ctx, lnp, io.df, io.ln2_part + (size_t)blk * 2 * D, bias + kBiasL2, qtok0, b0, last,
-                     sm.big, qtok1);
+    ln_bwd_lds(sm.h, sm.ctx, lnp, io.df, io.ln2_part + (size_t)blk * 2 * D, bias + kBiasL2, qtok0, b0, last,
+               sm.big, qtok1);
     BTR(TB + 1);
     __syncthreads();
     BTR(TB + 2);
@@ -2927,8 +2722,8 @@ __device__ void bwd_layer_split(Smem& sm, const float* __restrict__ P, const flo
     __syncthreads();
     BTR(TB + 6);
     // LN1 backward: sm.ctx -> dz1 planes in sm.h
-    ln_bwd_lds<true>(sm.ctx, sm.h, lnp, io.dz1, io.ln1_part + (size_t)blk * 2 * D, bias + kBiasOut, qtok0, b0, last,
-                     sm.big, qtok1);
+    ln_bwd_lds(sm.ctx, sm.h, lnp, io.dz1, io.ln1_part + (size_t)blk * 2 * D, bias + kBiasOut, qtok0, b0, last,
+               sm.big, qtok1);
     BTR(TB + 7);
     __syncthreads();
     BTR(TB + 8);
@@ -2952,7 +2747,7 @@ __device__ void bwd_layer_split(Smem& sm, const float* __restrict__ P, const flo
     for (int c = 0; c < 2; ++c) {
         [[maybe_unused]] HPre<2> pw;
         if constexpr (MODE == kBwdFull) pw = hprefetch<2>(PT, sWin, 3 * D, 16 * wv, 64 * c);
-        attn_bwd_chunk<last, true>(sm, ap, c, sm.scr, qsel, io.dqkv, b0, MODE == kBwdPos ? kvc : nullptr, blk);
+        attn_bwd_chunk<last>(sm, ap, c, sm.scr, qsel, io.dqkv, b0, MODE == kBwdPos ? kvc : nullptr, blk);
         __syncthreads();
         BTR(TB + 11 + 2 * c);
         if (tid_x() < 3 * 64) {  // in_proj bias partial of the chunk: the 8 wave rows of sm.scr
@@ -2999,197 +2794,17 @@ __device__ void bwd_layer_split(Smem& sm, const float* __restrict__ P, const flo
     __syncthreads();
     BTR(TB + 15);
 }
-
-// ln2_pre: this layer's LN2-backward operands, already loaded by the caller (nullptr: load here);
-// next_load: issues the next phase's global loads behind this layer's last weight loads.
-// MODE (the position-split training step, K7 below): kBwdFull = the whole layer; kBwdNoDx = stop after
-// the attention backward (dqkv rows and bias partials written; no W_in^T GEMM, no residual -- the
-// per-position kernels form dL/d(layer input)); kBwdPos = a full layer for the 16 query tokens of
-// ONE window position (tokens [qt, qt + 16), [b * 5 + s] rows, partial row prow): its dq rows go to
-// dqkv, its contributions to every position's dk / dv to kvc ([prow][80 tokens][dk 128 | dv 128]).
-// SP (kBwdFull only): every dX GEMM as split products on the f16 MFMA -- A = the transposed split
-// copies (PT + kTSplit), B = planes the producing epilogue writes: df (LN2 backward -> sm.ctx), du
-// (-> sm.big / sm.h), dz1 (LN1 backward -> sm.h), dq | dk | dv (attention backward -> sm.big, rows of
-// kLdbP halves, attn_out2); the residual terms read back from planes are x1 + 2^-11 x2.
-template <int trunk, int layer, bool last, int TB, class F = NoHook, int MODE = kBwdFull, bool SP = false>
-__device__ void bwd_layer(Smem& sm, const float* __restrict__ P, const float* __restrict__ PT, const BwdLayerIO& io,
-                          int b0, EmbBwdPre* ep = nullptr, const float* e_emb = nullptr, const float* xg = nullptr,
-                          const LnBwdPre* ln2_pre = nullptr, F next_load = F{}, int qt = 0, int prow = -1,
-                          float* __restrict__ kvc = nullptr) {
-    constexpr int liT = (trunk == kActorTrunk ? 0 : 1 + layer) * kLayerT;  // this layer's packedT offset
+// K6 and K7's B1 / B2 call bwd_layer through this forwarder, which carries the defaults and the
+// layer's first trace stamp. As layer_tail_fwd, the extra call level only fixes the inlining nesting:
+// the code objects of k_policy_backward, k_ps_b1 and k_ps_b2 depend on it (called directly: the same
+// instructions in another order). Fold it away only together with a same-box benchmark of them.
+template <int trunk, int layer, bool last, int TB, class F = NoHook, int MODE = kBwdFull>
+__device__ void bwd_layer_fwd(Smem& sm, const float* __restrict__ P, const float* __restrict__ PT, const BwdLayerIO& io,
+                              int b0, EmbBwdPre* ep = nullptr, const float* e_emb = nullptr, const float* xg = nullptr,
+                              const LnBwdPre* ln2_pre = nullptr, F next_load = F{}, int qt = 0, int prow = -1,
+                              float* __restrict__ kvc = nullptr) {
     BTR(TB);
-    static_assert(MODE != kBwdPos || !last, "position split: full layers only");
-    constexpr int CTQ = (last || MODE == kBwdPos) ? 1 : S;
-    constexpr int DQ = depth<CTQ>();
-    const int qtok0 = last ? (S - 1) * SPW : (MODE == kBwdPos ? qt : 0);
-    const int qtok1 = qtok0 + SPW * CTQ;
-    const int qsel = MODE == kBwdPos ? qt / SPW : -1;
-    const float* WinT = PT + kTWin;
-    const float* WoT = PT + kTWo;
-    const float* W1T = PT + kTW1;
-    const float* W2T = PT + kTW2;
-    const int wv = tid_x() >> 6, l = lane_id(), i16 = l & 15, g = l >> 4;
-    const int fo = 16 * wv + 4 * g;  // this lane's 4 output features of a 16-row tile of wave wv
-    const int blk = prow >= 0 ? prow : b0 / SPW;  // this workgroup's partial rows
-    float* bias = io.bpart + (size_t)blk * kBiasPart;  // this workgroup's bias partials
-
-    if constexpr (SP) {
-        bwd_layer_split<trunk, layer, last, TB, F, MODE>(sm, P, PT, io, b0, ep, e_emb, xg, ln2_pre, next_load, liT, qt,
-                                                         prow, kvc);
-        return;
-    } else {
-    // LN2 backward: sm.h -> sm.ctx (= df)
-    APre<DQ> pa = prefetch<DQ>(W2T, D, 16 * wv, 0);
-    LnBwdPre lnp;
-    if (ln2_pre) lnp = *ln2_pre;
-    else ln_bwd_load(lnp, io.xhat2, io.rstd2, P + kOffs.o[layer_param(trunk, layer, N2W)], qtok0, b0, last, qtok1);
-    ln_bwd_lds(sm.h, sm.ctx, lnp, io.df, io.ln2_part + (size_t)blk * 2 * D, bias + kBiasL2, qtok0, b0, last,
-               sm.big, qtok1);
-    BTR(TB + 1);
-    __syncthreads();
-    BTR(TB + 2);
-    // du = relu'(u) (W2^T df): 256 hidden features, wave wv owns tiles 16 wv (-> big) and 128 + 16 wv (-> h)
-    // the next GEMM's first weight blocks are loaded before each tile's du stores (a load issued
-    // behind a store burst waits for the whole burst)
-    APre<DQ> pb;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int row = 128 * t + 16 * wv;
-        f32x4 acc[CTQ], uu[CTQ];  // u (for the ReLU mask) loaded ahead of the GEMM
-#pragma unroll
-        for (int ct = 0; ct < CTQ; ++ct)
-            uu[ct] = ld4(io.u + (size_t)orow(qtok0 + 16 * ct + i16, b0, last) * FF + row + 4 * g);
-        zero(acc);
-        if (t == 0) {
-            gemm_tile<CTQ, DQ>(acc, pa, W2T, D, row, 0, sm.ctx, LDH, qtok0);
-            pb = prefetch<DQ>(W2T, D, 128 + 16 * wv, 0);
-        } else {
-            gemm_tile<CTQ, DQ>(acc, pb, W2T, D, row, 0, sm.ctx, LDH, qtok0);
-            pa = prefetch<DQ>(W1T, FF, 16 * wv, 0);
-        }
-        float* lds = t ? sm.h : sm.big;
-        f32x4 sd = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ct = 0; ct < CTQ; ++ct) {
-            const int tok = qtok0 + 16 * ct + i16;
-            const size_t r = (size_t)orow(tok, b0, last);
-            const f32x4 u = uu[ct];
-            f32x4 d = acc[ct];
-            d.x = u.x > 0.f ? d.x : 0.f; d.y = u.y > 0.f ? d.y : 0.f;
-            d.z = u.z > 0.f ? d.z : 0.f; d.w = u.w > 0.f ? d.w : 0.f;
-            dy_st4(io.du + r * FF + row + 4 * g, d);
-            st4(lds + tok * LDH + fo, d);
-            sd += d;
-        }
-        // linear1 bias partial: sum over the tokens (the 16 lanes of a row, then the column tiles)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sd[e] = row16_sum(sd[e]);
-        if (i16 == 0) st4(bias + kBiasL1 + row + 4 * g, sd);
-    }
-    BTR(TB + 3);
-    __syncthreads();
-    BTR(TB + 4);
-    // dh1 = df + W1^T du (K = 256: hidden 0-127 in big, 128-255 in h) -> sm.ctx in place
-    {
-        f32x4 acc[CTQ];
-        zero(acc);
-        gemm_tile<CTQ, DQ>(acc, pa, W1T, FF, 16 * wv, 0, sm.big, LDF, qtok0);
-        gemm_tile<CTQ, DQ>(acc, prefetch<DQ>(W1T, FF, 16 * wv, 128), W1T, FF, 16 * wv, 128, sm.h, LDH, qtok0);
-#pragma unroll
-        for (int ct = 0; ct < CTQ; ++ct) {
-            float* q = sm.ctx + (qtok0 + 16 * ct + i16) * LDH + fo;
-            st4(q, acc[ct] + ld4(q));
-        }
-    }
-    pa = prefetch<DQ>(WoT, D, 16 * wv, 0);
-    // LN1 backward's operands, then chunk 0's Q / K / V for the attention backward: their HBM
-    // latency hides under the residual pass / barrier and LN1 backward
-    ln_bwd_load(lnp, io.xhat1, io.rstd1, P + kOffs.o[layer_param(trunk, layer, N1W)], qtok0, b0, last, qtok1);
-    AttnPre ap;
-    attn_bwd_load<last>(ap, io.qkv, 0, b0, qsel);
-    BTR(TB + 5);
-    __syncthreads();
-    BTR(TB + 6);
-    // LN1 backward: sm.ctx -> sm.h (= dz1)
-    ln_bwd_lds(sm.ctx, sm.h, lnp, io.dz1, io.ln1_part + (size_t)blk * 2 * D, bias + kBiasOut, qtok0, b0, last,
-               sm.big, qtok1);
-    BTR(TB + 7);
-    __syncthreads();
-    BTR(TB + 8);
-    // d(attention output) = Wo^T dz1 -> sm.ctx
-    {
-        f32x4 acc[CTQ];
-        zero(acc);
-        gemm_tile<CTQ, DQ>(acc, pa, WoT, D, 16 * wv, 0, sm.h, LDH, qtok0);
-#pragma unroll
-        for (int ct = 0; ct < CTQ; ++ct) st4(sm.ctx + (qtok0 + 16 * ct + i16) * LDH + fo, acc[ct]);
-    }
-    BTR(TB + 9);
-    __syncthreads();
-    BTR(TB + 10);
-    // attention backward per chunk of 4 heads, dh_in += Win^T [dq | dk | dv] of the chunk (K = 3 x 64)
-    constexpr bool kDx = MODE == kBwdFull;
-    f32x4 acc[S];
-    zero(acc);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        [[maybe_unused]] APre<2> pw;
-        if constexpr (kDx) pw = prefetch<2>(WinT, 3 * D, 16 * wv, 64 * c);
-        attn_bwd_chunk<last>(sm, ap, c, sm.scr, qsel);
-        __syncthreads();
-        BTR(TB + 11 + 2 * c);
-        if (tid_x() < 3 * 64) {  // in_proj bias partial of the chunk: the 8 wave rows of sm.scr
-            const int i = tid_x();
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v += sm.scr[w * 192 + i];
-            bias[kBiasIn + (i >> 6) * D + 64 * c + (i & 63)] = v;
-        }
-        // first weight blocks of the chunk's K and V parts, loaded ahead of the stores below (the
-        // vector memory counter retires in order: loads behind a store burst wait for it)
-        [[maybe_unused]] APre<2> pw1, pw2;
-        if constexpr (kDx) {
-            pw1 = prefetch<2>(WinT, 3 * D, 16 * wv, D + 64 * c);
-            pw2 = prefetch<2>(WinT, 3 * D, 16 * wv, 2 * D + 64 * c);
-        }
-        // dq | dk | dv of the chunk -> dqkv rows: 256-byte row segments, float4 per thread
-        for (int i = tid_x(); i < TOK * 48; i += NTHR) {
-            const int tok = i / 48, r = i - tok * 48, part = r >> 4, q = r & 15;
-            if (part == 0 && (tok < qtok0 || tok >= qtok1)) continue;  // dq only on the query rows
-            const f32x4 v = ld4(sm.big + tok * LDB + part * 64 + 4 * q);
-            if (MODE == kBwdPos && part > 0)  // this query position's share of every position's dk / dv
-                st4(kvc + ((size_t)blk * TOK + tok) * 2 * D + (part - 1) * D + 64 * c + 4 * q, v);
-            else
-                dy_st4(io.dqkv + (size_t)trow(tok, b0) * 3 * D + part * D + 64 * c + 4 * q, v);
-        }
-        if constexpr (kDx) {
-            if (last) {  // dq is zero outside the query tile: Win_q^T dq only for column tile 4
-                f32x4 a1[1] = {acc[S - 1]};
-                gemm_tile<1, 2, 4>(a1, pw, WinT, 3 * D, 16 * wv, 64 * c, sm.big, LDB, (S - 1) * SPW);
-                acc[S - 1] = a1[0];
-            } else {
-                gemm_tile<S, 2, 4>(acc, pw, WinT, 3 * D, 16 * wv, 64 * c, sm.big, LDB, 0);
-            }
-            gemm_tile<S, 2, 4>(acc, pw1, WinT, 3 * D, 16 * wv, D + 64 * c, sm.big + 64, LDB, 0);
-            gemm_tile<S, 2, 4>(acc, pw2, WinT, 3 * D, 16 * wv, 2 * D + 64 * c, sm.big + 128, LDB, 0);
-        }
-        if (c == 0) attn_bwd_load<last>(ap, io.qkv, 1, b0, qsel);  // behind every weight load of the chunk
-        if (c == 0) __syncthreads();  // big is rewritten by chunk 1
-        BTR(TB + 12 + 2 * c);
-    }
-    if constexpr (!kDx) return;
-    if (layer == 0 && ep) embed_bwd_load(*ep, e_emb, xg, b0);
-    next_load();
-    // + dz1 on the rows that carried the residual -> sm.h
-#pragma unroll
-    for (int ct = 0; ct < S; ++ct) {
-        const int tok = 16 * ct + i16;
-        float* q = sm.h + tok * LDH + fo;
-        st4(q, tok >= qtok0 ? acc[ct] + ld4(q) : acc[ct]);
-    }
-    __syncthreads();
-    BTR(TB + 15);
-    }
+    bwd_layer<trunk, layer, last, TB, F, MODE>(sm, P, PT, io, b0, ep, e_emb, xg, ln2_pre, next_load, qt, prow, kvc);
 }
 
 // Embedding backward from sm.h = dL/d(h0) (80 tokens): h0 = relu(We x + be) + pos. Thread =
@@ -3426,7 +3041,7 @@ __global__ __launch_bounds__(NTHR) void k_policy_backward(const float* __restric
         __syncthreads();
         BTR(53);
         EmbBwdPre ep;
-        bwd_layer<kActorTrunk, 0, true, 36, NoHook, kBwdFull, kBwdSplit>(sm, P, PT, io.L[0], b0, &ep, io.e[0], io.xg);
+        bwd_layer_fwd<kActorTrunk, 0, true, 36, NoHook, kBwdFull>(sm, P, PT, io.L[0], b0, &ep, io.e[0], io.xg);
         embed_bwd(sm, ep, io.epart + (size_t)blk * 2 * kEmbPart, 57);
         BTR(54);
     };
@@ -3447,11 +3062,11 @@ __global__ __launch_bounds__(NTHR) void k_policy_backward(const float* __restric
         auto hook = [&] {
             ln_bwd_load(l2, io.L[1].xhat2, io.L[1].rstd2, P + kOffs.o[layer_param(kCriticTrunk, 0, N2W)], 0, b0, false);
         };
-        bwd_layer<kCriticTrunk, 1, true, 4, decltype(hook), kBwdFull, kBwdSplit>(sm, P, PT + 2 * kLayerT, io.L[2], b0,
-                                                                              nullptr, nullptr, nullptr, nullptr, hook);
+        bwd_layer_fwd<kCriticTrunk, 1, true, 4, decltype(hook), kBwdFull>(sm, P, PT + 2 * kLayerT, io.L[2], b0,
+                                                                          nullptr, nullptr, nullptr, nullptr, hook);
         EmbBwdPre ep;
-        bwd_layer<kCriticTrunk, 0, false, 20, NoHook, kBwdFull, kBwdSplit>(sm, P, PT + 1 * kLayerT, io.L[1], b0, &ep,
-                                                                         io.e[1], io.xg, &l2);
+        bwd_layer_fwd<kCriticTrunk, 0, false, 20, NoHook, kBwdFull>(sm, P, PT + 1 * kLayerT, io.L[1], b0, &ep,
+                                                                    io.e[1], io.xg, &l2);
         embed_bwd(sm, ep, io.epart + ((size_t)blk * 2 + 1) * kEmbPart);
         __syncthreads();
         BTR(52);
@@ -3496,7 +3111,8 @@ __device__ __forceinline__ void ps_rows_in(float* dst, int lds, const float* __r
 }
 
 // Embedding of window position s (transformer_net.py:57-59): h = relu(W_e x + b_e) + pos[s] -> sm.h
-// rows 16 s + p and the e / h0 workspace rows; wave w computes features [16 w, 16 w + 16).
+// rows 16 s + p, the planes of h into sm.ctx (ps_inproj's operand) and the e / h0 workspace rows;
+// wave w computes features [16 w, 16 w + 16).
 // The embedding's global operands (ps_embed_load: issued by k_ps_f1 before the window gather).
 struct PsEmbPre {
     f32x4 a, bb, pp;
@@ -3514,7 +3130,6 @@ __device__ __forceinline__ PsEmbPre ps_embed_load(const float* __restrict__ P, i
     r.pp = ld4(P + kOffs.o[trunk + POS] + s * D + 16 * wv + 4 * g);
     return r;
 }
-template <bool PL = false>  // PL: also the planes of h into sm.ctx (ps_inproj_split's operand)
 __device__ void ps_embed(Smem& sm, const PsEmbPre& ep, float* __restrict__ e_out, float* __restrict__ h_out, int b0,
                          int s, int ti) {
     const int l = lane_id(), i16 = l & 15, g = l >> 4, wv = tid_x() >> 6;
@@ -3527,31 +3142,17 @@ __device__ void ps_embed(Smem& sm, const PsEmbPre& ep, float* __restrict__ e_out
     e.x = fmaxf(e.x, 0.f); e.y = fmaxf(e.y, 0.f); e.z = fmaxf(e.z, 0.f); e.w = fmaxf(e.w, 0.f);
     const f32x4 v = e + pp;
     st4(sm.h + (s * SPW + i16) * LDH + 16 * wv + 4 * g, v);
-    if constexpr (PL)  // scaled per token (its window row's range)
-        hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw((s * SPW + i16), 16 * wv + 4 * g),
-                     v * e_sc_v(sm.rtab[kRtE + 2 * ti], sm.rtab[kRtE + 2 * ti + 1], sm.tmax[s * SPW + i16]).sc);
+    // scaled per token (its window row's range)
+    hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw((s * SPW + i16), 16 * wv + 4 * g),
+                 v * e_sc_v(sm.rtab[kRtE + 2 * ti], sm.rtab[kRtE + 2 * ti + 1], sm.tmax[s * SPW + i16]).sc);
     const size_t r = (size_t)trow(s * SPW + i16, b0);
     st4(e_out + r * D + 16 * wv + 4 * g, e);
     st4(h_out + r * D + 16 * wv + 4 * g, v);
 }
 
-// in_proj rows [16 tile0, 384) of the 16 tokens of position s (sm.h rows 16 s + p) -> qkv rows
-// (Q = rows 0-127, K = 128-255, V = 256-383 of a [b * 5 + s][384] row), bias added.
-__device__ void ps_inproj(Smem& sm, const float* __restrict__ W, const float* __restrict__ bias,
-                          float* __restrict__ qkv, int tile0, int s, int b0) {
-    const int l = lane_id(), i16 = l & 15, g = l >> 4, wv = tid_x() >> 6;
-    const size_t r = (size_t)trow(s * SPW + i16, b0);
-    for (int t = tile0 + wv; t < 3 * D / 16; t += NW) {  // wave-uniform
-        const int row = 16 * t;
-        const f32x4 bb = ld4(bias + row + 4 * g);
-        f32x4 acc[1];
-        zero(acc);
-        gemm_tile<1, 4>(acc, prefetch<4>(W, D, row, 0), W, D, row, 0, sm.h, LDH, s * SPW);
-        st4(qkv + r * 3 * D + row + 4 * g, acc[0] + bb);
-    }
-}
-
-// ps_inproj as split products: the operand planes of the 16 tokens at X rows 16 s + p, W's split copy at soff.
+// in_proj rows [16 tile0, 384) of the 16 tokens of position s -> qkv rows (Q = rows 0-127, K = 128-255,
+// V = 256-383 of a [b * 5 + s][384] row), bias added, as split products: the operand planes of the 16
+// tokens at X rows 16 s + p, W's split copy at soff.
 // Every weight block and bias of the wave's (at most 3) row tiles is loaded in one round
 // (ps_inproj_load, which a caller issues ahead of the operand's producer): one exposed L2 round trip
 // instead of one per tile -- the same MFMA sequence per tile, so the same sums.
@@ -3572,7 +3173,7 @@ __device__ __forceinline__ void ps_inproj_load(PsInPre& r, const float* __restri
     }
 }
 // inv: 2^s of the operand at this lane's token (the caller's: layer 0 per token, layer 1 static)
-__device__ void ps_inproj_split(const PsInPre& pre, const float* __restrict__ P, int soff, float* __restrict__ qkv,
+__device__ void ps_inproj(const PsInPre& pre, const float* __restrict__ P, int soff, float* __restrict__ qkv,
                                 int tile0, int s, int b0, const _Float16* X, float inv) {
     const int l = lane_id(), i16 = l & 15, g = l >> 4, wv = tid_x() >> 6;
     const size_t r = (size_t)trow(s * SPW + i16, b0);
@@ -3627,8 +3228,8 @@ __device__ __forceinline__ void ps_qkv_store(Smem& sm, const QkvPre& r, int s) {
     }
 }
 // the attention of both chunks (K7 F2 / F3): chunk 1's Q | K | V loads overlap chunk 0's attention
-// (PLANES: the output's planes scaled for layer `layer` of trunk `trunk`, P's range table)
-template <bool PLANES, int trunk, int layer>
+// (the output's planes scaled for layer `layer` of trunk `trunk`)
+template <int trunk, int layer>
 __device__ __forceinline__ void ps_attention(Smem& sm, const float* __restrict__ qkv, int s, int b0,
                                              const float* __restrict__ P) {
     QkvPre r;
@@ -3636,11 +3237,11 @@ __device__ __forceinline__ void ps_attention(Smem& sm, const float* __restrict__
     ps_qkv_store(sm, r, s);
     __syncthreads();
     ps_qkv_load(r, qkv, 1, s, b0);
-    attention_chunk<PLANES, trunk, layer>(sm, 0, s, 1, P);
+    attention_chunk<trunk, layer>(sm, 0, s, 1, P);
     __syncthreads();
     ps_qkv_store(sm, r, s);
     __syncthreads();
-    attention_chunk<PLANES, trunk, layer>(sm, 1, s, 1, P);
+    attention_chunk<trunk, layer>(sm, 1, s, 1, P);
     __syncthreads();
 }
 
@@ -3656,23 +3257,18 @@ __global__ __launch_bounds__(NTHR) void k_ps_f1(const float* __restrict__ P, con
     // every global operand of the embedding and of the in_proj GEMM first: their L2 round trip
     // overlaps the window gather's
     const PsEmbPre ep = ps_embed_load(P, trunk, s);
-    [[maybe_unused]] PsInPre wp;
-    if constexpr (kPsSplit) ps_inproj_load(wp, P, soff, P + kOffs.o[layer_param(trunk, 0, INB)], tile0);
+    PsInPre wp;
+    ps_inproj_load(wp, P, soff, P + kOffs.o[layer_param(trunk, 0, INB)], tile0);
     gather_windows<true>(sm, states, B, io, b0, r == 0, P + kRangeOff);  // one workgroup per block writes the rows
     load_rtab(sm, P);  // behind the gather's loads (its arithmetic waits on nothing they need)
     __syncthreads();
     // the step's derived scales, once: F2 / F3 and the weight-gradient GEMM read them (TrainIO::rtab_out)
     if (blockIdx.x == 0 && tid_x() < kRtN && io.rtab_out) io.rtab_out[tid_x()] = sm.rtab[tid_x()];
-    ps_embed<kPsSplit>(sm, ep, io.e[critic ? 1 : 0], io.h0[critic ? 1 : 0], b0, s, critic ? 1 : 0);
+    ps_embed(sm, ep, io.e[critic ? 1 : 0], io.h0[critic ? 1 : 0], b0, s, critic ? 1 : 0);
     __syncthreads();
-    if constexpr (kPsSplit) {
-        const float m = sm.tmax[s * SPW + (lane_id() & 15)];
-        ps_inproj_split(wp, P, soff, io.L[critic ? 1 : 0].qkv, tile0, s, b0, reinterpret_cast<const _Float16*>(sm.ctx),
-                        critic ? e_sc<kCriticTrunk>(sm, m).inv : e_sc<kActorTrunk>(sm, m).inv);
-    } else {
-        ps_inproj(sm, P + kOffs.o[layer_param(trunk, 0, INW)], P + kOffs.o[layer_param(trunk, 0, INB)],
-                  io.L[critic ? 1 : 0].qkv, critic || s == S - 1 ? 0 : D / 16, s, b0);
-    }
+    const float m = sm.tmax[s * SPW + (lane_id() & 15)];
+    ps_inproj(wp, P, soff, io.L[critic ? 1 : 0].qkv, tile0, s, b0, reinterpret_cast<const _Float16*>(sm.ctx),
+              critic ? e_sc<kCriticTrunk>(sm, m).inv : e_sc<kActorTrunk>(sm, m).inv);
 }
 
 __global__ __launch_bounds__(NTHR) void k_ps_f2(const float* __restrict__ P, const TrainIO io) {
@@ -3682,10 +3278,9 @@ __global__ __launch_bounds__(NTHR) void k_ps_f2(const float* __restrict__ P, con
     const int s = critic ? r : S - 1, ti = critic ? 1 : 0;
     // the out-projection's first weight blocks ahead of the attention (whose Q | K | V loads and
     // barriers then cover their round trip)
-    [[maybe_unused]] HPre<2> po;
-    if constexpr (kPsSplit)
-        po = hprefetch<2>(P, critic ? split_slot(layer_param(kCriticTrunk, 0, OUTW)) : split_slot(layer_param(kActorTrunk, 0, OUTW)),
-                          D, 16 * wv, 0);
+    HPre<2> po;
+    po = hprefetch<2>(P, critic ? split_slot(layer_param(kCriticTrunk, 0, OUTW)) : split_slot(layer_param(kActorTrunk, 0, OUTW)),
+                      D, 16 * wv, 0);
     // the block's window-row maxima (F1's) first: reduced once the rows below have landed (the
     // vector memory counter retires in order), not waited for ahead of their loads
     const float a0v = a0f_load(io.tmax + (size_t)b0 * S);
@@ -3697,42 +3292,27 @@ __global__ __launch_bounds__(NTHR) void k_ps_f2(const float* __restrict__ P, con
     for (int k = 0; k < 8; ++k) ec[k] = io.rtab_out[kRtE + k];
     const float xm = a0f_finish(sm, a0v, ec, ec + 4);
     if (r == 0 && tid_x() == 0 && io.xmax) io.xmax[blk] = xm;  // the block's range for the weight gradients
-    if (critic) ps_attention<kPsSplit, kCriticTrunk, 0>(sm, io.L[ti].qkv, s, b0, P);
-    else ps_attention<kPsSplit, kActorTrunk, 0>(sm, io.L[ti].qkv, s, b0, P);
-    [[maybe_unused]] APre<4> ph;
-    if constexpr (kPsSplit) {  // the layer tails and the next in_proj as split products
-        if (critic) {
-            // layer 1's in_proj weights and biases are issued before LN2 (the tail's hook), behind
-            // every weight load of the tail
-            constexpr int s1 = split_slot(layer_param(kCriticTrunk, 1, INW));
-            const int tile0 = s == S - 1 ? 0 : D / 16;
-            PsInPre wp;
-            auto hook = [&] { ps_inproj_load(wp, P, s1, P + kOffs.o[layer_param(kCriticTrunk, 1, INB)], tile0); };
-            layer_tail_split<kCriticTrunk, 0, false, true, decltype(hook), 1>(sm, P, po, io.L[1], b0, hook, s * SPW);
-            __syncthreads();
-            // layer 1 (pruned) of this position: K | V, and Q at position 4, from LN2's planes in sm.h
-            ps_inproj_split(wp, P, s1, io.L[2].qkv, tile0, s, b0, reinterpret_cast<const _Float16*>(sm.h),
-                            op_sc<kCriticTrunk, 0, kOpLn2>(sm).inv);
-            return;
-        }
-        auto hook = [&] {  // the head's weights before LN2
-            if (wv < 4) ph = prefetch<4>(P + kOffs.o[kActorHead], D, 16 * wv, 0);
-        };
-        layer_tail_split<kActorTrunk, 0, true, true, decltype(hook)>(sm, P, po, io.L[0], b0, hook);
-    } else {
-        if (critic) {
-            const APre<4> po = prefetch<4>(P + kOffs.o[layer_param(kCriticTrunk, 0, OUTW)], D, 16 * wv, 0);
-            layer_tail<kCriticTrunk, 0, false, true, NoHook, 1>(sm, P, po, io.L[1], b0, NoHook{}, s * SPW);
-            __syncthreads();
-            // layer 1 (pruned) of this position: K | V, and Q at position 4
-            ps_inproj(sm, P + kOffs.o[layer_param(kCriticTrunk, 1, INW)], P + kOffs.o[layer_param(kCriticTrunk, 1, INB)],
-                      io.L[2].qkv, s == S - 1 ? 0 : D / 16, s, b0);
-            return;
-        }
-        const APre<4> po = prefetch<4>(P + kOffs.o[layer_param(kActorTrunk, 0, OUTW)], D, 16 * wv, 0);
-        layer_tail<kActorTrunk, 0, true, true>(sm, P, po, io.L[0], b0);
-        if (wv < 4) ph = prefetch<4>(P + kOffs.o[kActorHead], D, 16 * wv, 0);
+    if (critic) ps_attention<kCriticTrunk, 0>(sm, io.L[ti].qkv, s, b0, P);
+    else ps_attention<kActorTrunk, 0>(sm, io.L[ti].qkv, s, b0, P);
+    APre<4> ph;  // the actor head's weights
+    if (critic) {
+        // layer 1's in_proj weights and biases are issued before LN2 (the tail's hook), behind
+        // every weight load of the tail
+        constexpr int s1 = split_slot(layer_param(kCriticTrunk, 1, INW));
+        const int tile0 = s == S - 1 ? 0 : D / 16;
+        PsInPre wp;
+        auto hook = [&] { ps_inproj_load(wp, P, s1, P + kOffs.o[layer_param(kCriticTrunk, 1, INB)], tile0); };
+        layer_tail<kCriticTrunk, 0, false, true, decltype(hook), 1>(sm, P, po, io.L[1], b0, hook, s * SPW);
+        __syncthreads();
+        // layer 1 (pruned) of this position: K | V, and Q at position 4, from LN2's planes in sm.h
+        ps_inproj(wp, P, s1, io.L[2].qkv, tile0, s, b0, reinterpret_cast<const _Float16*>(sm.h),
+                  op_sc<kCriticTrunk, 0, kOpLn2>(sm).inv);
+        return;
     }
+    auto hook = [&] {  // the head's weights before LN2
+        if (wv < 4) ph = prefetch<4>(P + kOffs.o[kActorHead], D, 16 * wv, 0);
+    };
+    layer_tail<kActorTrunk, 0, true, true, decltype(hook)>(sm, P, po, io.L[0], b0, hook);
     __syncthreads();
     head_mlp<kActorHead, 2>(sm, P, ph, sm.logits);
     store_hidden(sm, io.z[0], b0);
@@ -3747,23 +3327,17 @@ __global__ __launch_bounds__(NTHR) void k_ps_f3(const float* __restrict__ P, con
     __shared__ __attribute__((aligned(16))) Smem sm;
     const int b0 = blockIdx.x * SPW, wv = tid_x() >> 6;
     // the out-projection's first weight blocks ahead of the attention (as k_ps_f2)
-    [[maybe_unused]] HPre<2> po;
-    if constexpr (kPsSplit) po = hprefetch<2>(P, split_slot(layer_param(kCriticTrunk, 1, OUTW)), D, 16 * wv, 0);
+    HPre<2> po;
+    po = hprefetch<2>(P, split_slot(layer_param(kCriticTrunk, 1, OUTW)), D, 16 * wv, 0);
     ps_mask(sm, io.mask, b0);
     ps_rows_in(sm.h, LDH, io.L[1].h2, D, 0, D, S - 1, b0);  // layer 1's input (residual) at position 4
     load_rtab_ready(sm, io.rtab_out);  // F1's derived table, behind the loads above
-    ps_attention<kPsSplit, kCriticTrunk, 1>(sm, io.L[2].qkv, S - 1, b0, P);
+    ps_attention<kCriticTrunk, 1>(sm, io.L[2].qkv, S - 1, b0, P);
     APre<4> ph;
-    if constexpr (kPsSplit) {  // the residual is in sm.h (ps_rows_in): PSX = 2
-        auto hook = [&] {  // the head's weights before LN2
-            if (wv < 4) ph = prefetch<4>(P + kOffs.o[kCriticHead], D, 16 * wv, 0);
-        };
-        layer_tail_split<kCriticTrunk, 1, true, true, decltype(hook), 2>(sm, P, po, io.L[2], b0, hook);
-    } else {
-        const APre<4> po = prefetch<4>(P + kOffs.o[layer_param(kCriticTrunk, 1, OUTW)], D, 16 * wv, 0);
-        layer_tail<kCriticTrunk, 1, true, true>(sm, P, po, io.L[2], b0);
+    auto hook = [&] {  // the head's weights before LN2
         if (wv < 4) ph = prefetch<4>(P + kOffs.o[kCriticHead], D, 16 * wv, 0);
-    }
+    };
+    layer_tail<kCriticTrunk, 1, true, true, decltype(hook), 2>(sm, P, po, io.L[2], b0, hook);  // residual in sm.h: PSX = 2
     __syncthreads();
     head_mlp<kCriticHead, 1>(sm, P, ph, sm.value);
     store_hidden(sm, io.z[1], b0);
@@ -3787,30 +3361,26 @@ __global__ __launch_bounds__(NTHR) void k_ps_b1(const float* __restrict__ P, con
     if (role == 2) {  // critic: head.0, layer 1 (pruned) down to its dqkv rows
         head_input_grad(sm, PT + kHeadT + D * HID, sm.ctx + 64);
         __syncthreads();
-        bwd_layer<kCriticTrunk, 1, true, 4, NoHook, kBwdNoDx, kPsSplit>(sm, P, PT + 2 * kLayerT, io.L[2], b0, nullptr, nullptr,
-                                                                 nullptr, nullptr, NoHook{}, 0, blk * S);
+        bwd_layer_fwd<kCriticTrunk, 1, true, 4, NoHook, kBwdNoDx>(sm, P, PT + 2 * kLayerT, io.L[2], b0, nullptr, nullptr,
+                                                                  nullptr, nullptr, NoHook{}, 0, blk * S);
     } else {  // actor: head.0, layer 0 (pruned) down to its dqkv rows
         head_input_grad(sm, PT + kHeadT, sm.z);
         __syncthreads();
-        bwd_layer<kActorTrunk, 0, true, 36, NoHook, kBwdNoDx, kPsSplit>(sm, P, PT, io.L[0], b0, nullptr, nullptr, nullptr,
-                                                                nullptr, NoHook{}, 0, blk * S);
+        bwd_layer_fwd<kActorTrunk, 0, true, 36, NoHook, kBwdNoDx>(sm, P, PT, io.L[0], b0, nullptr, nullptr, nullptr,
+                                                                  nullptr, NoHook{}, 0, blk * S);
     }
 }
 
 // The 16 [dq | dk | dv] rows of position s -> sm.big rows p (stride LDQ); with_q = false: a pruned
 // layer off its query position (dq never written there: zero)
-// (kPsSplit: as the two fp16 planes of ps_dx's split products, both in one row of 2 LDQ halves,
-// plane 2 at + 3 D: conflict-free ds_read_b128 like the fp32 LDQ rows)
+// (as the two fp16 planes of ps_dx's split products, both in one row of 2 LDQ halves, plane 2 at
+// + 3 D: conflict-free ds_read_b128)
 __device__ __forceinline__ void ps_big_store(Smem& sm, int p, int q, const f32x4 v) {
-    if constexpr (kPsSplit) {
-        _Float16* bp = reinterpret_cast<_Float16*>(sm.big);
-        f16x4 a, b;
-        f16_split4(v, a, b);
-        *reinterpret_cast<f16x4*>(bp + p * 2 * LDQ + 4 * q) = a;  // [p][plane 1 | plane 2 | pad]
-        *reinterpret_cast<f16x4*>(bp + p * 2 * LDQ + 3 * D + 4 * q) = b;
-    } else {
-        st4(sm.big + p * LDQ + 4 * q, v);
-    }
+    _Float16* bp = reinterpret_cast<_Float16*>(sm.big);
+    f16x4 a, b;
+    f16_split4(v, a, b);
+    *reinterpret_cast<f16x4*>(bp + p * 2 * LDQ + 4 * q) = a;  // [p][plane 1 | plane 2 | pad]
+    *reinterpret_cast<f16x4*>(bp + p * 2 * LDQ + 3 * D + 4 * q) = b;
 }
 __device__ __forceinline__ void ps_dqkv_in(Smem& sm, const float* __restrict__ dqkv, bool with_q, int s, int b0) {
     for (int i = tid_x(); i < SPW * 96; i += NTHR) {
@@ -3840,27 +3410,16 @@ __device__ void ps_dx(Smem& sm, const PsDxPre& pw, const float* __restrict__ Win
                       int s) {
     const int l = lane_id(), i16 = l & 15, g = l >> 4, wv = tid_x() >> 6;
     const int fo = 16 * wv + 4 * g;
-    f32x4 acc[1];
+    f32x4 acc[1], lo[1];  // WinT + kTSplit: the split copy of this layer's in_proj^T
     zero(acc);
-    if constexpr (kPsSplit) {  // WinT + kTSplit: the split copy of this layer's in_proj^T
-        f32x4 lo[1];
-        zero(lo);
-        const _Float16* bp = reinterpret_cast<const _Float16*>(sm.big);
+    zero(lo);
+    const _Float16* bp = reinterpret_cast<const _Float16*>(sm.big);
 #pragma unroll
-        for (int part = 0; part < 3; ++part) {
-            if (part == 0 && !with_q) continue;
-            hgemm_tile<1, 4, 4, 2 * LDQ, 3 * D>(acc, lo, pw.w[part], WinT, kTSplit, 3 * D, 16 * wv, part * D,
-                                                bp + part * D, 0);
-        }
-        acc[0] += lo[0] * kLoScale;
-    } else {
-#pragma unroll
-        for (int part = 0; part < 3; ++part) {
-            if (part == 0 && !with_q) continue;
-            gemm_tile<1, 4>(acc, prefetch<4>(WinT, 3 * D, 16 * wv, part * D), WinT, 3 * D, 16 * wv, part * D,
-                            sm.big + part * D, LDQ, 0);
-        }
+    for (int part = 0; part < 3; ++part) {
+        if (part == 0 && !with_q) continue;
+        hgemm_tile<1, 4, 4, 2 * LDQ, 3 * D>(acc, lo, pw.w[part], WinT, kTSplit, 3 * D, 16 * wv, part * D, bp + part * D, 0);
     }
+    acc[0] += lo[0] * kLoScale;
     f32x4 v = acc[0];
     if (has_res) v += pw.res;  // (wave-uniform) the residual ps_dx_load read
     st4(sm.h + (s * SPW + i16) * LDH + fo, v);
@@ -3952,8 +3511,8 @@ __global__ __launch_bounds__(NTHR) void k_ps_b2(const float* __restrict__ P, con
     }
     ps_dx(sm, pw, WinT, q4, q4, s);
     __syncthreads();
-    bwd_layer<kCriticTrunk, 0, false, 20, NoHook, kBwdPos, kPsSplit>(sm, P, PT + kLayerT, io.L[1], b0, nullptr, nullptr, nullptr,
-                                                              nullptr, NoHook{}, s * SPW, prow, kvc);
+    bwd_layer_fwd<kCriticTrunk, 0, false, 20, NoHook, kBwdPos>(sm, P, PT + kLayerT, io.L[1], b0, nullptr, nullptr, nullptr,
+                                                               nullptr, NoHook{}, s * SPW, prow, kvc);
 }
 
 __global__ __launch_bounds__(NTHR) void k_ps_b3(const float* __restrict__ PT, const BwdIO io,
@@ -4011,6 +3570,10 @@ int policy_loss_partials(const TrainIO& io, int Bm, hipStream_t st) {
 }
 
 int policy_forward_ps(const float* packed, const float* states, const TrainIO& io, int Bm, hipStream_t st) {
+    if (!io.rtab_out) {  // F2 / F3 load F1's derived range table from it
+        set_error("policy_forward_ps: TrainIO::rtab_out is NULL");
+        return UAVHIP_EINVAL;
+    }
     const int nblk = Bm / SPW;
     hipLaunchKernelGGL(k_ps_f1, dim3(nblk * 10), dim3(NTHR), 0, st, packed, states, Bm, io);
     if (const int rc = check_launch("k_ps_f1")) return rc;
@@ -4038,9 +3601,10 @@ int policy_backward_train(const float* packed, const float* packedT, const BwdIO
 
 
 // flat (state_dict order, plain layout) -> packed (GEMM weights in MFMA fragment order) and, when
-// packedT is given, the backward's transposed copies: per layer [in_proj^T | out_proj^T |
-// linear1^T | linear2^T], then head.0^T of both heads, with packedT[((r/16) * K/16 + k/16) * 256 +
-// (r%16 + 16 ((k%16)/4)) * 4 + k%4] = W[k][r]. One thread per output float4.
+// packedT is given, the backward's fp32 transposed copies: the slots of the layers' [in_proj^T |
+// out_proj^T | linear1^T | linear2^T] (NaN: the backward reads their split copies, k_policyT_split),
+// then head.0^T of both heads, with packedT[((r/16) * K/16 + k/16) * 256 + (r%16 + 16 ((k%16)/4)) * 4
+// + k%4] = W[k][r]. One thread per output float4.
 __global__ __launch_bounds__(256) void k_policy_pack(const float* __restrict__ flat, float* __restrict__ packed,
                                                      float* __restrict__ packedT) {
     constexpr int nq = kOffs.o[kNumParams] / 4;
@@ -4060,38 +3624,26 @@ __global__ __launch_bounds__(256) void k_policy_pack(const float* __restrict__ f
             const int kb = blk % KB, rt = blk / KB;
             src = kOffs.o[lo] + (16 * rt + (lane & 15)) * K + 16 * kb + 4 * (lane >> 4);
         }
-        // the training pack (packedT given): the split-copy weights' fp32 copies are never read
-        const bool dead = !kTrainF32LayerCopies && packedT && K != 0 && split_slot(lo) >= 0;
+        // the training pack (packedT given): the training kernels read the layer GEMM weights only
+        // through their split copies, so the fp32 copies are filled with NaN (a read would poison
+        // every output) and k_adam does not refresh them
+        const bool dead = packedT && K != 0 && split_slot(lo) >= 0;
         *reinterpret_cast<f32x4*>(packed + f) =
             dead ? f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")}
                  : *reinterpret_cast<const f32x4*>(flat + src);
         return;
     }
     if (!packedT || i >= nq + kPackedTFloats / 4) return;
-    if (!kTrainF32LayerCopies && 4 * (i - nq) < kHeadT) {  // a layer weight's fp32 transposed copy: dead
+    if (4 * (i - nq) < kHeadT) {  // a layer weight's fp32 transposed copy: never read (NaN, as above)
         *reinterpret_cast<f32x4*>(packedT + 4 * (i - nq)) =
             f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
         return;
     }
+    // head.0 weight [64][128] of the actor / critic head, transposed
     const int idx = 4 * (i - nq);
-    int src, m, Rt, Kt;
-    if (idx < kHeadT) {
-        const int li = idx / kLayerT, loc = idx - li * kLayerT;
-        const int trunk = li == 0 ? kActorTrunk : kCriticTrunk, layer = li == 2 ? 1 : 0;
-        int which, base;
-        if (loc < kTWo) { which = INW; base = kTWin; Rt = D; Kt = 3 * D; }
-        else if (loc < kTW1) { which = OUTW; base = kTWo; Rt = D; Kt = D; }
-        else if (loc < kTW2) { which = L1W; base = kTW1; Rt = D; Kt = FF; }
-        else { which = L2W; base = kTW2; Rt = FF; Kt = D; }
-        src = kOffs.o[layer_param(trunk, layer, which)];
-        m = loc - base;
-    } else {  // head.0 weight [64][128] of the actor / critic head, transposed
-        const int h = (idx - kHeadT) / (D * HID);
-        src = kOffs.o[h ? kCriticHead : kActorHead];
-        m = idx - kHeadT - h * D * HID;
-        Rt = D;
-        Kt = HID;
-    }
+    const int h = (idx - kHeadT) / (D * HID);
+    const int src = kOffs.o[h ? kCriticHead : kActorHead], m = idx - kHeadT - h * D * HID;
+    constexpr int Rt = D, Kt = HID;
     const int lane = (m >> 2) & 63, blk = m >> 8, KBt = Kt / 16;
     const int kb = blk % KBt, rt = blk / KBt;
     const int r = 16 * rt + (lane & 15), k = 16 * kb + 4 * (lane >> 4);

@@ -46,8 +46,9 @@ enum { POS = 0, EMB_W = 1, EMB_B = 2 };
 enum { INW = 0, INB, OUTW, OUTB, L1W, L1B, L2W, L2B, N1W, N1B, N2W, N2B };
 __host__ __device__ constexpr int layer_param(int trunk, int l, int which) { return trunk + 3 + kLayerParams * l + which; }
 
-// ---- split copies (inference forward only): the GEMM weights over all 80 tokens that run on the
-// f16 matrix cores as fp32-accurate split products (policy.hip, hgemm_tile): the critic's layer-0
+// ---- split copies: the GEMM weights that run on the f16 matrix cores as fp32-accurate split
+// products (policy.hip, hgemm_tile) -- every encoder-layer GEMM, listed in the order the
+// kernels adopted them (the order fixes the packed offsets): the critic's layer-0
 // out-projection and FFN, and its layer-1 in_proj (K / V of every token, Q of position 4); the
 // layer-0 in_proj of both trunks for the rollout's window-row ring (the new row's Q | K | V); and the
 // out-projection and FFN of both trunks' pruned top layers (the 16 tokens of position 4). Each weight
@@ -75,6 +76,15 @@ constexpr int split_slot(int q) {
         if (kSplitParam[i] == q) return kSplitOffs.o[i];
     return -1;
 }
+// Every encoder-layer GEMM runs on its split copy (the kernels have no f32 path for them; the one
+// exception is the non-ring inference forward's layer-0 in_proj, which also keeps its fp32 copy).
+constexpr bool all_layer_gemms_split() {
+    for (int li = 0; li < 3; ++li)  // actor layer 0, critic layers 0 and 1
+        for (int w = INW; w <= L2W; w += 2)  // INW, OUTW, L1W, L2W
+            if (split_slot(layer_param(li ? kCriticTrunk : kActorTrunk, li == 2, w)) < 0) return false;
+    return true;
+}
+static_assert(all_layer_gemms_split(), "all twelve layer GEMM weights are in kSplitParam");
 
 // ---- range table (DESIGN.md 4a "range"): after the split copies. The split products carry each
 // activation operand as fp16 planes, exact to 2^-22 only for |x| in [2^-14, 65504], so every operand

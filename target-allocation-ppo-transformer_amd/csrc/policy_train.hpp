@@ -25,7 +25,9 @@ struct TrainIO {
     float* tmax;                 // [R] max |x_k| of each window row (layer 0's operand range; K7 F2 reads it)
     float* xmax;                 // [Bm/16] max over each 16-sample block's window rows (the weight-gradient
                                  // GEMM's range of the layer-0 operands; nullable)
-    float* rtab_out;             // [kRtN] the forward's derived scales (policy_layout.hpp kRtOp ..; nullable)
+    float* rtab_out;             // [kRtN] the forward's derived scales (policy_layout.hpp kRtOp ..). Required by
+                                 // the position split (k_ps_f2 / f3 read F1's table through it:
+                                 // policy_forward_ps rejects NULL); the fused forward skips the export on NULL
     float *e[2], *h0[2];         // [R][128] actor, critic embeddings (post-ReLU) and layer inputs
     TrainLayerIO L[3];           // actor L0 (pruned), critic L0 (full), critic L1 (pruned)
     float* z[2];                 // [Bm][64] relu(head.0) of the actor / critic head
@@ -106,11 +108,10 @@ constexpr int kPackedTFloats = kHeadT + 2 * D * HID;
 // the weight's packedT offset
 constexpr int kTSplit = kPackedTFloats;
 constexpr int kPackedTAllFloats = kTSplit + kHeadT;
-// The training kernels read the encoder GEMM weights only through their split copies (policy.hip
-// kTrainSplit / kBwdSplit / kPsSplit): the trainer's fp32 fragment-order copies of those weights
-// (packed at their kOffs slots, packedT below kHeadT) are dead. policy_pack_train fills them with
-// NaN (a read would poison every output) and k_adam does not refresh them.
-constexpr bool kTrainF32LayerCopies = false;
+// The training kernels read the encoder GEMM weights only through their split copies: the trainer's
+// fp32 fragment-order copies of those weights (packed at their kOffs slots, packedT below kHeadT)
+// are dead. policy_pack_train fills them with NaN (a read would poison every output) and k_adam
+// does not refresh them.
 
 // flat parameters -> packed (forward) and packedT (backward) in one launch
 int policy_pack_train(const float* flat, float* packed, float* packedT, hipStream_t st);

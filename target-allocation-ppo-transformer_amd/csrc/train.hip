@@ -386,10 +386,10 @@ __global__ __launch_bounds__(256) void k_adam(const AdamArgs a) {
         return;
     }
     // packed: row i of [NR][NC] in fragment order, float4 = columns j..j+3 (not for the weights the
-    // training kernels read only through their split copies: policy_train.hpp kTrainF32LayerCopies)
+    // training kernels read only through their split copies: their fp32 slots stay NaN, policy_train.hpp)
     const int loc = 4 * item, i = loc / NC, j = loc - i * NC;
     const int sb = kAdamBlocks.sbase[blockIdx.x];
-    if (kTrainF32LayerCopies || sb < 0)
+    if (sb < 0)
         *reinterpret_cast<f32x4*>(a.packed + off + (((i >> 4) * (NC >> 4) + (j >> 4)) * 64 + (i & 15) +
                                                       16 * ((j & 15) >> 2)) * 4) = p;
     // the split copy (policy_layout.hpp kSplitParam): the fp16 planes of these four weights, lane
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(256) void k_adam(const AdamArgs a) {
     const f32x4 col = {tile[(4 * rq) * NC + jt], tile[(4 * rq + 1) * NC + jt], tile[(4 * rq + 2) * NC + jt],
                        tile[(4 * rq + 3) * NC + jt]};
     const int tb = kAdamBlocks.tbase[blockIdx.x];
-    if (kTrainF32LayerCopies || tb >= kHeadT)
+    if (tb >= kHeadT)  // head.0^T; a layer weight's fp32 transposed slot stays NaN
         *reinterpret_cast<f32x4*>(a.packedT + tb + (((jt >> 4) * (NR >> 4) + (it >> 4)) * 64 + (jt & 15) +
                                                     16 * ((it & 15) >> 2)) * 4) = col;
     if (tb < kHeadT) {  // a layer weight: its transposed split copy (W^T[jt][it .. it + 3], halves it % 8 ..)
