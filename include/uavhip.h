@@ -204,7 +204,13 @@ int uavhip_env_reset(const uavhip_env* env, const uint8_t* mask, int32_t episode
  * auto_reset != 0: a finished env is reset in-kernel (state-only, or a fresh on-device scene
  * every full_reset_period episodes) and obs_out carries the NEW episode's first window;
  * auto_reset == 0: obs_out is all zeros for a finished env (the reference returns zeros(14),
- * uav_env.py:188-189) and stepping it again only sets istate[ERROR]. */
+ * uav_env.py:188-189) and stepping it again only sets istate[ERROR].
+ * The device env step (step_once / gstep) has a third auto_reset value, UAVHIP_STEP_HOLD: as 0, but
+ * a finished env is HELD -- stepping it again is not an error (istate[ERROR] is not set), its state
+ * keeps every value, and the step reports a zero window, reward 0, done 1. It is compiled into the
+ * decode kernel only (uavhip_decode_steps, which always runs with it: episodes of different lengths
+ * in one launch); this entry point takes it as any other nonzero value. */
+#define UAVHIP_STEP_HOLD 2
 int uavhip_env_step(const uavhip_env* env, const int8_t* actions, int32_t T, int32_t auto_reset,
                     float* obs_out, double* reward, uint8_t* done, double* info, uavhip_stream_t stream);
 
@@ -356,6 +362,40 @@ int uavhip_rollout_steps(const uavhip_policy* policy, const uavhip_env* env, flo
                          uint64_t offset_stride, const uint64_t* offset_dev, int8_t* actions, float* logp,
                          float* value, int32_t auto_reset, double* reward, uint8_t* done, double* info,
                          uavhip_stream_t stream);
+
+/* ---------------------------------------------------------------- inference (decode) */
+
+/* Decode an allocation with a trained policy: up to n_max steps of every env in ONE launch, each
+ * step the ACTOR trunk and head of the window-row forward, an action, and the env step with
+ * UAVHIP_STEP_HOLD -- no critic, no logp / value, no trajectory, no auto-reset. The critic's ring
+ * rows are neither read nor written (a later forward of both trunks on this rowproj needs fill).
+ *  - action of env e: greedy (a = l1 > l0, a tie gives 0) iff greedy_stride > 0 and
+ *    e % greedy_stride == 0; else sampled as uavhip_rollout_steps samples, Philox counter
+ *    offset + t * offset_stride + (offset_dev ? *offset_dev : 0) + e at the call's step t = 0, 1, ..
+ *    (greedy_stride 1: all greedy; 0: all sampled; K: replica 0 of each scene of K replicas);
+ *  - a finished env (istate[UAV_IDX] >= N) is held, and a workgroup (16 envs) leaves the step
+ *    loop once all of its envs are finished;
+ *  - obs2 [2][E][5][14] f32: the windows ping-pong, step `step` + t reads slot (step + t) & 1 and
+ *    writes the other; the caller puts the current windows into slot step & 1;
+ *  - step: the ring step of the first decoded step (as uavhip_rollout_steps; also picks the
+ *    window slot). A continuation call passes the steps decoded so far and fill = 1;
+ *  - steps [E] int32 (required): steps taken by env e since its reset, ADDED to (the caller zeroes
+ *    it at a reset); finished [E] u8 (required): written; actions [n_max][E] int8 (nullable): the
+ *    action trace of this call, -1 in the rows at or past the env's end; ep_return [E] f64
+ *    (nullable): sum of rewards including the goal reward, ADDED to in step order.
+ * N, M <= 64; f32 observations. */
+int uavhip_decode_steps(const uavhip_policy* policy, const uavhip_env* env, float* obs2, float* rowproj,
+                        int32_t step, int32_t n_max, int32_t fill, int32_t greedy_stride, uint64_t seed,
+                        uint64_t offset, uint64_t offset_stride, const uint64_t* offset_dev, int8_t* actions,
+                        int32_t* steps, uint8_t* finished, double* ep_return, uavhip_stream_t stream);
+
+/* Best of K: envs are K replicas of E / K scenes, scene-major (e = s * K + k). Per scene s, the
+ * FINISHED replica with the largest dstate[J] (lowest k on a tie): best [S] int32 = k, or -1 when no
+ * replica finished (then J = 0, covered = 0, assignment all -1); J [S] f64; covered [S] int32 =
+ * istate[N_COVERED]; assignment [S][N] int32 = tgt_id (of the replica's ACTIVE scene buffer) of each
+ * UAV's target, -1 for none. Every output is required. */
+int uavhip_select_best(const uavhip_env* env, int32_t K, int32_t* best, double* J, int32_t* covered,
+                       int32_t* assignment, uavhip_stream_t stream);
 
 /* ---------------------------------------------------------------- PPO update (K5) */
 

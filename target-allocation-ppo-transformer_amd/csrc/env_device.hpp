@@ -581,12 +581,15 @@ __device__ void write_info(const EnvRegs<TPL>& R, const uavhip_env& env, double 
 
 // One UAVEnv.step (uav_env.py:295-435) on register state. No scene generation on this path: a
 // full reset flips to the pre-generated spare scene (scene_buffers == 2).
-template <int TPL, bool LT = false>
+// auto_reset: 0 / nonzero as uavhip_env_step documents; HOLD instantiations (the decode kernel) also
+// take UAVHIP_STEP_HOLD: as 0, but stepping a finished env is no error -- it is held: R keeps every
+// value (R.err included), the outputs are a zero window, reward 0, done 1.
+template <int TPL, bool LT = false, bool HOLD = false>
 __device__ void step_once(EnvRegs<TPL>& R, const uavhip_env& env, int e, int lane, int a, int auto_reset,
                           float* obs_o, double* rew_o, uint8_t* done_o, double* info_o) {
     const int N = env.N, M = env.M;
     if (R.u >= N) {  // stepping a finished env: the reference raises IndexError (:296)
-        R.err |= 1;
+        if (!(HOLD && auto_reset == UAVHIP_STEP_HOLD)) R.err |= 1;  // held: the env waits, untouched
         if (obs_o) write_obs(obs_o, 0.0f, 0.0f, lane, obs_f16(env));
         if (lane == 0) {
             if (rew_o) *rew_o = 0.0;
@@ -668,7 +671,7 @@ __device__ void step_once(EnvRegs<TPL>& R, const uavhip_env& env, int e, int lan
         load_cur_pair<TPL, LT>(R, env);
         push_obs(R, lane);
         if (obs_o) write_obs(obs_o, R.w0, R.w1, lane, obs_f16(env));
-    } else if (auto_reset) {
+    } else if (auto_reset && !(HOLD && auto_reset == UAVHIP_STEP_HOLD)) {
         R.ep += 1;
         const int P = env.full_reset_period;
         bool flipped = false;

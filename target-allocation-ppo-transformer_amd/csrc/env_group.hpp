@@ -433,8 +433,8 @@ __device__ void gstore_delta(const GRegs& R, const uavhip_env& env, int e, int j
     if (j < kObs - 2 * L) w[2 * L + j] = R.w2;
 }
 
-// One UAVEnv.step (uav_env.py:295-435) of this group's env (envdev::step_once).
-template <bool TAB = true>
+// One UAVEnv.step (uav_env.py:295-435) of this group's env (envdev::step_once; HOLD as there).
+template <bool TAB = true, bool HOLD = false>
 __device__ void gstep(GRegs& R, const uavhip_env& env, int e, int j, int a, int auto_reset, float* obs_o,
                       double* rew_o, uint8_t* done_o, double* info_o) {
     const int N = env.N, M = env.M;
@@ -442,7 +442,7 @@ __device__ void gstep(GRegs& R, const uavhip_env& env, int e, int j, int a, int 
         rew_o = nullptr; done_o = nullptr; info_o = nullptr;
     }
     if (R.u >= N) {  // stepping a finished env: the reference raises IndexError (:296)
-        R.err |= 1;
+        if (!(HOLD && auto_reset == UAVHIP_STEP_HOLD)) R.err |= 1;  // held: the env waits, untouched
         if (obs_o) gwrite_obs(obs_o, R, j, true, obs_f16(env));
         if (j == 0) {
             if (rew_o) *rew_o = 0.0;
@@ -535,7 +535,7 @@ __device__ void gstep(GRegs& R, const uavhip_env& env, int e, int j, int a, int 
     if (!done) {
         if (obs_o) gwrite_obs(obs_o, R, j, false, obs_f16(env));
         GTR(45);
-    } else if (auto_reset) {
+    } else if (auto_reset && !(HOLD && auto_reset == UAVHIP_STEP_HOLD)) {
         R.ep += 1;
         const int P = env.full_reset_period;
         bool flipped = false;

@@ -53,7 +53,59 @@ __global__ __launch_bounds__(256) void k_episode_stats(const double* __restrict_
     for (int i = 0; i < UAVHIP_EP_COUNT; ++i) ae[i] = a[i];
 }
 
+// Best of K (uavhip_select_best): one wave per scene. Every lane walks the scene's K replicas
+// (e = s * K + k; wave-uniform loads) for the finished one with the largest J, the lowest k on a tie;
+// lane u then writes UAV u's target id of that replica.
+__global__ __launch_bounds__(256) void k_select_best(uavhip_env env, int K, int S, int* __restrict__ best,
+                                                     double* __restrict__ J, int* __restrict__ covered,
+                                                     int* __restrict__ assignment) {
+    const int s = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6), lane = threadIdx.x & (kWave - 1);
+    if (s >= S) return;
+    int kb = -1;
+    double jb = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const long long e = (long long)s * K + k;
+        if (env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_UAV_IDX] < env.N) continue;  // not finished
+        const double j = env.dstate[e * UAVHIP_DST_COUNT + UAVHIP_DST_J];
+        if (kb < 0 || j > jb) {
+            kb = k;
+            jb = j;
+        }
+    }
+    const long long e = (long long)s * K + (kb < 0 ? 0 : kb);
+    const int* is = env.istate + e * UAVHIP_IST_COUNT;
+    if (lane == 0) {
+        best[s] = kb;
+        J[s] = jb;
+        covered[s] = kb < 0 ? 0 : is[UAVHIP_IST_N_COVERED];
+    }
+    for (int u = lane; u < env.N; u += kWave) {
+        int id = -1;
+        if (kb >= 0) {
+            const int t = env.assigned[e * env.N + u];
+            const long long sb = (env.scene_buffers == 2 ? (long long)(is[UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+            if (t >= 0) id = env.tgt_id[sb * env.M + t];
+        }
+        assignment[(long long)s * env.N + u] = id;
+    }
+}
+
 }  // namespace uavhip
+
+extern "C" int uavhip_select_best(const uavhip_env* env, int32_t K, int32_t* best, double* J, int32_t* covered,
+                                  int32_t* assignment, uavhip_stream_t stream) {
+    using namespace uavhip;
+    if (const int rc = validate_env(env, true)) return rc;
+    if (K <= 0 || env->E % K != 0 || !best || !J || !covered || !assignment) {
+        set_error("uavhip_select_best: K=%d must be > 0 and divide E=%d, and best/J/covered/assignment non-NULL", K,
+                  env->E);
+        return UAVHIP_EINVAL;
+    }
+    const int S = env->E / K;
+    hipLaunchKernelGGL(k_select_best, dim3((S + 3) / 4), dim3(256), 0, (hipStream_t)stream, *env, (int)K, S, best, J,
+                       covered, assignment);
+    return check_launch("k_select_best");
+}
 
 extern "C" int uavhip_episode_stats(const double* reward, const uint8_t* done, const int8_t* action,
                                     const double* info, const float* value, int32_t T, int32_t E, double* acc,

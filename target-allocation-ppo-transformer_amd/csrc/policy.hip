@@ -1838,20 +1838,25 @@ enum { kEnvGrp = 1, kEnvWave = 2, kEnvBoth = 3 };
 // VONLY (inference, ROWS): the critic trunk and head only -- the value of each window, nothing
 // else (the rollout's bootstrap V(s_T), uavhip_policy_value_rows); the actor's ring row of the step
 // is not written.
-template <bool TR, bool ROWS, int ENV, bool VONLY = false>
+// AONLY (inference, ROWS, ENV): the mirror image, the actor trunk and head only and then the env step
+// (k_decode_steps) -- the critic's ring rows are neither read nor written, no value; env b decodes
+// greedily (a = l1 > l0) iff greedy_stride > 0 and b % greedy_stride == 0, else it samples.
+template <bool TR, bool ROWS, int ENV, bool VONLY = false, bool AONLY = false>
 __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __restrict__ P, const float* __restrict__ states,
                                              int B, const int8_t* __restrict__ actions_in, uint64_t seed,
                                              uint64_t offset, const uint64_t* __restrict__ offset_dev,
                                              int8_t* __restrict__ action_out, float* __restrict__ logp_out,
                                              float* __restrict__ value_out, float* __restrict__ ent_out,
                                              float* __restrict__ logits_out, const TrainIO& io, const RowIO& rio,
-                                             const uavhip_env& env, const EnvOut& eo, int bx) {
+                                             const uavhip_env& env, const EnvOut& eo, int bx,
+                                             [[maybe_unused]] int greedy_stride = 0) {
     static_assert(!(TR && ROWS), "the training forward recomputes every row");
     static_assert(!ENV || ROWS, "the fused env step follows the rollout forward");
     static_assert(!VONLY || (ROWS && !ENV && !TR), "value only: the inference ring forward");
+    static_assert(!AONLY || (ROWS && ENV && !TR && !VONLY), "actor only: the inference ring forward + env step");
     // training trunk split (TrainIO::split): role 1 = actor trunk + head, 2 = critic trunk + head
     // of sample block blk; role 0 = both (the rollout always)
-    int blk = bx, role = VONLY ? 2 : 0;
+    int blk = bx, role = VONLY ? 2 : AONLY ? 1 : 0;
     if constexpr (TR) {
         if (io.split) {
             role = blk < io.split ? 1 : 2;
@@ -1891,6 +1896,11 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             const u32x4 r = philox(u32x4{(uint32_t)c, (uint32_t)(c >> 32), 0x5eedu, 0x9e37u}, (uint32_t)seed,
                                    (uint32_t)(seed >> 32));
             sm.u01[pd] = u01f(r.x);
+            // actor only: a greedy env's draw is the sentinel -1 (u01f is never negative); decided
+            // here, where greedy_stride need not stay live across the forward
+            if constexpr (AONLY) {
+                if (greedy_stride > 0 && (b0 + pd) % greedy_stride == 0) sm.u01[pd] = -1.f;
+            }
         }
     }
     __syncthreads();
@@ -1906,6 +1916,12 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
     const int wv = TIDX() >> 6;
     const float* headw_a = P + kOffs.o[kActorHead];
     const float* headw_c = P + kOffs.o[kCriticHead];
+    // fused env step (ENV): two envs per wave side by side, state loads issued before the critic head
+    // (AONLY: before the actor head)
+    [[maybe_unused]] const bool env_grp =
+        (ENV & kEnvGrp) && env.N <= envgrp::L && env.M <= envgrp::L && b0 + 2 * wv + 1 < B;
+    [[maybe_unused]] envgrp::GRegs gR;
+    [[maybe_unused]] envgrp::GPending gq;
     // actor trunk (1 layer) + head
     if constexpr (ROWS) {
         if (do_actor) {
@@ -1958,17 +1974,19 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             __syncthreads();
             encoder_layer<kActorTrunk, 0, true, TR>(TID_C sm, P, pkv, io.L[0], b0);
         }
+        // actor only: the env step's state loads land while the actor head runs
+        if constexpr (AONLY && (ENV & kEnvGrp) && !kExpNoEnv) {
+            if (env_grp) {
+                const int le = tid_env() & 63;
+                envgrp::gload_issue(gR, gq, env, b0 + 2 * (int)(tid_env() >> 6) + (le >> 5), le & 31);
+            }
+        }
         if (wv < 4) ph = prefetch<kHd>(TID_C headw_a, D, 16 * wv, 0);
         __syncthreads();
         PTR(3);
         head_mlp<kActorHead, 2, kHd>(TID_C sm, P, ph, sm.logits);
     }  // do_actor
     PTR(4);
-    // fused env step (ENV): two envs per wave side by side, state loads issued before the critic head
-    [[maybe_unused]] const bool env_grp =
-        (ENV & kEnvGrp) && env.N <= envgrp::L && env.M <= envgrp::L && b0 + 2 * wv + 1 < B;
-    [[maybe_unused]] envgrp::GRegs gR;
-    [[maybe_unused]] envgrp::GPending gq;
     if (do_critic) {
         // critic trunk (2 layers) + head
         if constexpr (ROWS) {
@@ -2066,6 +2084,9 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
                     u = u01f(r.x);
                 }
                 a = u < p0 ? 0 : 1;
+                if constexpr (AONLY) {  // greedy decode: torch.argmax (a tie gives 0)
+                    if (kEarlyDraw ? u < 0.f : (greedy_stride > 0 && b % greedy_stride == 0)) a = l1 > l0;
+                }
             }
             if (action_out) action_out[b] = (int8_t)a;
             if (logp_out) logp_out[b] = a ? lp1 : lp0;
@@ -2101,8 +2122,9 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             R.win = sm.h + (2 * wve + g) * envgrp::kWin;
             envgrp::gload_finish(R, gq, env, e, j);
             PTR(61);
-            envgrp::gstep<false>(R, env, e, j, sm.mask[2 * wve + g], eo.auto_reset, obs_at(eo.obs, e, obs_f16(env)),
-                          eo.rew + e, eo.done + e, eo.info ? eo.info + (size_t)e * UAVHIP_INFO_COUNT : nullptr);
+            envgrp::gstep<false, AONLY>(R, env, e, j, sm.mask[2 * wve + g], eo.auto_reset, obs_at(eo.obs, e, obs_f16(env)),
+                          (AONLY && !eo.rew) ? nullptr : eo.rew + e,  // the decode's return is optional
+                          eo.done + e, eo.info ? eo.info + (size_t)e * UAVHIP_INFO_COUNT : nullptr);
             PTR(62);
             if constexpr (UAVHIP_EXP == 42) envgrp::gstore_regs(R, env, e, j);  // timing build: every entry
             else envgrp::gstore_delta(R, env, e, j);  // only the entries the step changed
@@ -2119,8 +2141,9 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
                 if (k == 1 && !two) break;
                 EnvRegs<1>& R = k ? R1 : R0;
                 const int e = e0 + k;
-                step_once<1, false>(R, env, e, lane, sm.mask[2 * wve + k], eo.auto_reset,
-                                    obs_at(eo.obs, e, obs_f16(env)), eo.rew + e, eo.done + e,
+                step_once<1, false, AONLY>(R, env, e, lane, sm.mask[2 * wve + k], eo.auto_reset,
+                                    obs_at(eo.obs, e, obs_f16(env)), (AONLY && !eo.rew) ? nullptr : eo.rew + e,
+                                    eo.done + e,
                                     eo.info ? eo.info + (size_t)e * UAVHIP_INFO_COUNT : nullptr);
                 store_regs(R, env, e, lane);
             }
@@ -2162,6 +2185,24 @@ struct StepSeq {
 int launch_rollout_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
                          const uint64_t* offset_dev, int8_t* actions, float* logp, float* value, const RowIO& rio,
                          const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream);
+// k_decode_steps' only parameter (uavhip_decode_steps; the same translation unit as k_rollout_steps)
+struct DecodeArgs {
+    const float* P;
+    float* obs2;  // [2][B][5][14]: step rio.g + t reads slot (rio.g + t) & 1 and writes the other
+    int B;
+    uint64_t seed, offset;
+    const uint64_t* offset_dev;
+    RowIO rio;
+    uavhip_env env;
+    int n_max, greedy_stride;
+    long long obs_stride;  // floats between the two slots (B * 5 * 14)
+    uint64_t off_stride;   // sampling counter advance per step
+    int8_t* actions;       // [n_max][B] (nullable)
+    int32_t* steps;        // [B]
+    uint8_t* finished;     // [B]; the env step's done flag of every step
+    double* ep_return;     // [B] (nullable); between the steps the env step's reward
+};
+int launch_decode_steps(const DecodeArgs& da, hipStream_t stream);
 #ifdef UAVHIP_STEPS_TU
 // All of the launch's arguments in one struct: the kernel's only parameter, so the kernarg
 // segment holds exactly this struct at offset 0.
@@ -2223,6 +2264,111 @@ int launch_rollout_steps(const float* P, float* obs, int B, uint64_t seed, uint6
     else
         hipLaunchKernelGGL(k_rollout_steps<kEnvWave>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
     return check_launch("k_rollout_steps");
+}
+
+// Decode (uavhip_decode_steps): k_rollout_steps' loop with the actor-only block (policy_block AONLY)
+// and UAVHIP_STEP_HOLD -- a finished env waits, untouched, and the workgroup leaves the loop once its
+// 16 envs are finished. The windows ping-pong between the two slots of obs2; nothing is kept per
+// step but the optional action trace. Wave 0's first 16 lanes keep each env's step count, return
+// and finished flag in LDS between the steps (one lane per env; the step's reward and done flag
+// come back through global memory, args.ep_return / args.finished, behind a workgroup barrier).
+// After a step: the envs' counters (wave 0's first 16 lanes), the trace row and the workgroup's
+// all-finished flag. The arguments are read through a kernarg pointer of its own, so that nothing
+// of the step's stays live across the forward for it.
+__device__ __forceinline__ void post_step(unsigned tid, Smem& sm, int t, double* s_ret, int* s_cnt, int* s_fin,
+                                          int* s_all) {
+    typedef const __attribute__((address_space(4))) DecodeArgs* kargs;
+    kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    int bx = blockIdx.x;
+    asm volatile("" : "+s"(ka), "+s"(bx));
+    const DecodeArgs& a = *(const DecodeArgs*)ka;
+    if (tid < SPW) {
+        const int p = tid, e = bx * SPW + p;
+        bool fin = true;
+        if (e < a.B) {
+            const bool was = s_fin[p] != 0;
+            if (!was) {
+                s_cnt[p] += 1;
+                if (a.ep_return) s_ret[p] = s_ret[p] + a.ep_return[e];  // this step's reward
+            }
+            if (a.actions) a.actions[(size_t)t * a.B + e] = was ? (int8_t)-1 : (int8_t)sm.mask[p];
+            fin = was || a.finished[e] != 0;
+            s_fin[p] = fin;
+        }
+        const unsigned m = (unsigned)ballot(fin) & 0xffffu;
+        if (p == 0) *s_all = m == 0xffffu;
+    }
+}
+template <int ENVP>
+__global__ __launch_bounds__(NTHR) void k_decode_steps(const DecodeArgs args) {
+    __shared__ __attribute__((aligned(16))) Smem sm;
+    __shared__ double s_ret[SPW];
+    __shared__ int s_cnt[SPW], s_fin[SPW], s_all;
+    if (threadIdx.x >= NTHR / 2) __builtin_amdgcn_s_setprio(1);
+    if (threadIdx.x == 0) g_tid_zero = 0;
+    load_rtab(TID_K sm, args.P);
+    if (threadIdx.x < SPW) {
+        const int p = threadIdx.x, e = blockIdx.x * SPW + p;
+        const bool fin = e >= args.B || args.env.istate[(long long)e * UAVHIP_IST_COUNT + UAVHIP_IST_UAV_IDX] >= args.env.N;
+        s_fin[p] = fin;
+        s_cnt[p] = 0;
+        s_ret[p] = (e < args.B && args.ep_return) ? args.ep_return[e] : 0.0;
+        const unsigned m = (unsigned)ballot(fin) & 0xffffu;
+        if (p == 0) s_all = m == 0xffffu;
+    }
+    int t = 0;
+    for (;;) {
+        __syncthreads();  // s_all; g_tid_zero; the previous step's LDS scratch and global stores
+        typedef const __attribute__((address_space(4))) DecodeArgs* kargs;
+        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+        int bx = blockIdx.x;
+        unsigned tid = threadIdx.x;
+        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
+        tid &= NTHR - 1;
+        const DecodeArgs& a = *(const DecodeArgs*)ka;
+        // workgroup-uniform: every wave reads the flag wave 0 wrote before the barrier
+        if (__builtin_amdgcn_readfirstlane(s_all) || t >= a.n_max) break;
+        const int slot = (a.rio.g + t) & 1;
+        const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
+        const EnvOut eo{UAVHIP_STEP_HOLD, a.obs2 + (slot ^ 1) * a.obs_stride, a.ep_return, a.finished, nullptr};
+        policy_block<false, true, ENVP, false, true>(tid, sm, a.P, a.obs2 + slot * a.obs_stride, a.B, nullptr, a.seed,
+                                                     a.offset + t * a.off_stride, a.offset_dev, nullptr, nullptr,
+                                                     nullptr, nullptr, nullptr, TrainIO{}, r, a.env, eo, bx,
+                                                     a.greedy_stride);
+        __syncthreads();  // the env step's reward / done stores; sm.mask still holds the actions
+        post_step(tid, sm, t, s_ret, s_cnt, s_fin, &s_all);
+        ++t;
+    }
+    // the envs' totals; the trace rows the workgroup did not run (the arguments through a kernarg
+    // pointer of their own again: loaded here, not kept from the prologue across the loop)
+    typedef const __attribute__((address_space(4))) DecodeArgs* kargs;
+    kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+    int bx = blockIdx.x;
+    unsigned tid = threadIdx.x;
+    asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
+    tid &= NTHR - 1;
+    const DecodeArgs& a = *(const DecodeArgs*)ka;
+    const int e0 = bx * SPW;
+    if (tid < SPW && e0 + (int)tid < a.B) {
+        const int p = tid, e = e0 + p;
+        a.steps[e] += s_cnt[p];
+        a.finished[e] = s_fin[p] != 0;
+        if (a.ep_return) a.ep_return[e] = s_ret[p];
+    }
+    if (a.actions) {
+        for (int i = tid; i < (a.n_max - t) * SPW; i += NTHR) {
+            const int e = e0 + i % SPW;
+            if (e < a.B) a.actions[(size_t)(t + i / SPW) * a.B + e] = -1;
+        }
+    }
+}
+int launch_decode_steps(const DecodeArgs& da, hipStream_t stream) {
+    // one env path per instantiation, chosen as launch_rollout_steps chooses
+    if (da.env.N <= envgrp::L && da.env.M <= envgrp::L && da.B % 2 == 0)
+        hipLaunchKernelGGL(k_decode_steps<kEnvGrp>, dim3((da.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, da);
+    else
+        hipLaunchKernelGGL(k_decode_steps<kEnvWave>, dim3((da.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, da);
+    return check_launch("k_decode_steps");
 }
 #endif  // UAVHIP_STEPS_TU
 
@@ -3937,7 +4083,40 @@ extern "C" int uavhip_rollout_steps(const uavhip_policy* policy, const uavhip_en
                                      *env, pol::EnvOut{(int)auto_reset, obs + stride, reward, done, info},
                                      pol::StepSeq{(int)n, stride, offset_stride}, (hipStream_t)stream);
 }
-#else   // the steps TU ends after k_rollout_steps
+
+// Inference: up to n_max actor-only steps of every env in one launch (k_decode_steps).
+extern "C" int uavhip_decode_steps(const uavhip_policy* policy, const uavhip_env* env, float* obs2, float* rowproj,
+                                   int32_t step, int32_t n_max, int32_t fill, int32_t greedy_stride, uint64_t seed,
+                                   uint64_t offset, uint64_t offset_stride, const uint64_t* offset_dev,
+                                   int8_t* actions, int32_t* steps, uint8_t* finished, double* ep_return,
+                                   uavhip_stream_t stream) {
+    if (const int rc = validate_env(env, true)) return rc;
+    const int32_t B = env->E;
+    if (const int rc = check_policy("uavhip_decode_steps", policy, obs2, B)) return rc;
+    if (env->N > 64 || env->M > 64 || (env->flags & UAVHIP_ENV_OBS_F16) || n_max <= 0 || greedy_stride < 0 || !steps ||
+        !finished) {
+        set_error("uavhip_decode_steps: N=%d, M=%d must be <= 64, observations f32, n_max=%d > 0, "
+                  "greedy_stride=%d >= 0 and steps/finished non-NULL", env->N, env->M, n_max, greedy_stride);
+        return UAVHIP_EINVAL;
+    }
+    if (!rowproj || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
+        set_error("uavhip_decode_steps: NULL rowproj, step=%d < 0 or E=%d above the ring's 32-bit offsets", step, B);
+        return UAVHIP_EINVAL;
+    }
+    const int grid = (B + pol::SPW - 1) / pol::SPW;
+    const pol::RowIO rio{rowproj, (int)B, (int)step};
+    const long long stride = (long long)B * pol::S * pol::IN;
+    if (fill) {
+        hipLaunchKernelGGL(pol::k_policy_rows_fill, dim3(grid > pol::kPposParts ? grid : pol::kPposParts), dim3(pol::NTHR), 0,
+                           (hipStream_t)stream, policy->weights, obs2 + (step & 1) * stride, rio);
+        if (const int rc = check_launch("k_policy_rows_fill")) return rc;
+    }
+    return pol::launch_decode_steps(pol::DecodeArgs{policy->weights, obs2, (int)B, seed, offset, offset_dev, rio, *env,
+                                                    (int)n_max, (int)greedy_stride, stride, offset_stride, actions,
+                                                    steps, finished, ep_return},
+                                    (hipStream_t)stream);
+}
+#else  // the steps TU ends after k_rollout_steps
 }  // namespace pol
 }  // namespace uavhip
 #endif  // !UAVHIP_STEPS_TU

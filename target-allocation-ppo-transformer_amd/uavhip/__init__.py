@@ -6,6 +6,7 @@
     gae                GAE + advantage normalisation on the GPU (gae.hip)
     RolloutEngine      T-step batched rollout (+ RCCL trajectory all-gather)
     PPOAgent           agents/ppo.py API
+    AllocationSolver   batched inference: actor-only decode to the episode end, best of K (solve.py)
     load_checkpoint    the reference's torch.save(state_dict) files, older architectures reported
 
 Importing this package loads libuavhip.so and raises if it is missing: there is no CPU fallback.
@@ -18,5 +19,17 @@ from .ppo import PPOAgent, gae  # noqa: F401
 from .rollout import RolloutEngine, Trajectory  # noqa: F401
 from .vec_env import VecUAVEnv  # noqa: F401
 
+
+
+def __getattr__(name):
+    # solve.py is also a command line (python -m uavhip.solve): imported on first use, so that runpy
+    # does not find it in sys.modules already
+    if name in ("Allocation", "AllocationSolver"):
+        from . import solve
+        return getattr(solve, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __all__ = ["LIB", "UavHipError", "Config", "cfg", "TransformerActorCritic", "pack_weights", "PPOAgent", "gae",
-           "RolloutEngine", "Trajectory", "VecUAVEnv", "load_checkpoint", "save_checkpoint"]
+           "RolloutEngine", "Trajectory", "VecUAVEnv", "load_checkpoint", "save_checkpoint", "Allocation",
+           "AllocationSolver"]

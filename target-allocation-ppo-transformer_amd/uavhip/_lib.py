@@ -23,6 +23,7 @@ STATE_DIM = 14
 OBS_FLOATS = SEQ_LEN * STATE_DIM
 MAX_N, MAX_M, MAX_OBSTACLES = 64, 128, 8
 ENV_ONE_PER_WAVE, ENV_OBS_F16, ENV_NO_REPLAY = 1, 2, 4  # uavhip_env.flags bits
+STEP_HOLD = 2  # UAVHIP_STEP_HOLD: the decode kernel's env-step mode (a finished env is held)
 
 PRM = dict(ZETA_D=0, K=1, C1=2, C2=3, C3=4, C4=5, OMEGA=6, ZETA_OBS=7)
 PRM_COUNT = 8
@@ -103,6 +104,10 @@ _SIGS = {
     "uavhip_rollout_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), _vp, _vp, _i32,
                                             _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
                                             _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "uavhip_decode_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _i32,
+                                           _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
+                                           _vp, _vp, _vp, _vp]),
+    "uavhip_select_best": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _vp, _vp, _vp, _vp, _vp]),
     "uavhip_ppo_workspace_floats": (ctypes.c_int64, [_i32]),
     "uavhip_ppo_step": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "uavhip_episode_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),

@@ -257,6 +257,39 @@ class TransformerActorCritic(nn.Module):
                                        ptr(value), int(bool(auto_reset)), ptr(rewards), ptr(dones), ptr(info),
                                        stream_handle()), "uavhip_rollout_steps")
 
+    def decode_steps(self, env, obs2, rowproj, step, fill, steps, finished, actions=None, ep_return=None,
+                     n_max=None, greedy_stride=1, seed=None, offset=0, offset_stride=0, offset_dev=None):
+        """uavhip_decode_steps: up to n_max actor-only steps of every env of VecUAVEnv `env` in one
+        launch (inference: no critic, no trajectory, finished envs held, a workgroup stops when its
+        envs are finished). obs2 [2][E][5][14] f32 ping-pong windows (slot step & 1 = the current
+        ones); steps [E] int32 and ep_return [E] f64 (optional) are added to, finished [E] u8 is
+        written, actions [n_max][E] int8 (optional) receives the trace (-1 past an env's end).
+        Env e is greedy iff greedy_stride > 0 and e % greedy_stride == 0, else it samples with
+        counters offset + t * offset_stride + e (+ *offset_dev)."""
+        if self._packed is None:
+            self.packed_weights()
+        E, dev = env.E, env.device
+        if actions is not None:
+            if actions.dim() != 2:
+                raise ValueError("actions: need an int8 [n_max][E] buffer")
+            n_max = actions.shape[0] if n_max is None else n_max
+            check_out(actions, "actions", torch.int8, (n_max, E), dev)
+        if n_max is None:
+            raise ValueError("decode_steps: pass n_max or an actions buffer")
+        check_out(obs2, "obs2", torch.float32, (2, E), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
+        if rowproj is not None and (rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or
+                                    rowproj.dtype != torch.float32 or not rowproj.is_contiguous()):
+            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
+        check_out(steps, "steps", torch.int32, (E,), dev)
+        check_out(finished, "finished", torch.uint8, (E,), dev)
+        check_out(ep_return, "ep_return", torch.float64, (E,), dev)
+        seed = self.sample_seed if seed is None else seed
+        check(LIB.uavhip_decode_steps(self._desc, env.desc, ptr(obs2), ptr(rowproj), int(step), int(n_max),
+                                      int(bool(fill)), int(greedy_stride), ctypes.c_uint64(seed),
+                                      ctypes.c_uint64(offset), ctypes.c_uint64(offset_stride), ptr(offset_dev),
+                                      ptr(actions), ptr(steps), ptr(finished), ptr(ep_return), stream_handle()),
+              "uavhip_decode_steps")
+
     @torch.no_grad()
     def get_action(self, state):
         """transformer_net.py:96-122 -> (action [B] int64, log_prob [B], value [B, 1], entropy [B])."""

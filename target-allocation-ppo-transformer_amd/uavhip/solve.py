@@ -1,0 +1,188 @@
+"""Batched allocation inference: a trained policy and a set of scenes in, allocations out.
+
+The reference's only inference tool is test_visualize.py: one scene, one sampled episode, on the
+CPU (policy.get_action -> env.step until done, then the UAVs' assigned_target_id and J). Here every
+scene is decoded on the GPU by uavhip_decode_steps -- the ACTOR trunk and head, an action and the
+env step per step, nothing else, every env until its own episode ends -- and, with samples = K > 1,
+K times: replica 0 of each scene greedily (argmax), the others by sampling, and
+uavhip_select_best keeps the replica with the largest objective J(X) (best-of-K, the usual way a
+learned constructive solver is used).
+
+    solver = AllocationSolver(policy, num_uavs=16, num_targets=32, samples=8)
+    alloc = solver.solve(num_scenes=4096, seed=0)       # or solve(scenes=[scene dicts])
+    alloc.assignment[s]   # [N] target id of each UAV (-1: none), alloc.J[s], alloc.covered[s]
+
+Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
+prints one JSON line (mean / best J, mean covered, mean steps, scenes/s).
+
+The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
+policy is not touched (the packed weights are shared through policy.packed_weights()).
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .config import cfg as default_cfg
+from .policy import rowproj_buffer
+from .vec_env import SCENE_KEYS_F64, VecUAVEnv
+
+
+@dataclass
+class Allocation:
+    """Result of AllocationSolver.solve (device tensors; .cpu() moves them to the host)."""
+    assignment: torch.Tensor    # [S, N] int32: the target id each UAV locked, -1 for none
+    J: torch.Tensor             # [S] f64: objective J(X) of the chosen replica (0 when none finished)
+    covered: torch.Tensor       # [S] int32: targets with at least one lock
+    best_replica: torch.Tensor  # [S] int32: index of the chosen replica, -1 when none finished
+    steps: torch.Tensor         # [S] int32: decode steps of the chosen replica
+    replica_J: torch.Tensor     # [S, K] f64: J of every replica as decoding left it
+    actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
+
+    def cpu(self):
+        return Allocation(*(None if t is None else t.cpu() for t in
+                            (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
+                             self.actions)))
+
+
+class AllocationSolver:
+    def __init__(self, policy, num_uavs, num_targets, num_nfz=None, num_interceptors=None, config=None, samples=1,
+                 device=None):
+        p0 = next(policy.parameters())
+        if p0.device.type != "cuda":
+            raise RuntimeError("AllocationSolver decodes on the GPU (HIP) only: move the policy to a cuda device")
+        self.policy = policy
+        self.device = torch.device(p0.device if device is None else device)
+        if self.device.type != "cuda":
+            raise RuntimeError("AllocationSolver decodes on the GPU (HIP) only")
+        self.cfg = config or default_cfg
+        self.N, self.M = int(num_uavs), int(num_targets)
+        if self.N > 64 or self.M > 64:
+            raise ValueError(f"the decode kernel needs N, M <= 64 (got {self.N}, {self.M})")
+        self.Kn, self.Ki = num_nfz, num_interceptors
+        self.K = int(samples)
+        if self.K < 1:
+            raise ValueError("samples must be >= 1")
+        self.env = None
+
+    def _size(self, S):
+        """The env of S * K replicas and the decode buffers (kept while S stays the same)."""
+        E = S * self.K
+        if self.env is None or self.env.E != E:
+            dev = self.device
+            self.env = VecUAVEnv(E, self.N, self.M, self.Kn, self.Ki, config=self.cfg, device=dev,
+                                 full_reset_period=0, scene_buffers=1)
+            self.obs2 = torch.zeros(2, E, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev)
+            self.rowproj = rowproj_buffer(E, dev)
+            self.steps = torch.zeros(E, dtype=torch.int32, device=dev)
+            self.finished = torch.zeros(E, dtype=torch.uint8, device=dev)
+            self.ep_return = torch.zeros(E, dtype=torch.float64, device=dev)
+        return self.env
+
+    def _load_host_scenes(self, env, scenes):
+        """VecUAVEnv.load_scenes for K replicas of each scene: the S scenes go up once, every scene
+        array is repeated K times scene-major (e = s * K + k), and the pair tables are scored once."""
+        S, K = len(scenes), self.K
+        if any(np.size(s["tgt_value"]) and float(np.min(s["tgt_value"])) < 0 for s in scenes):
+            env.desc.flags |= _lib.ENV_NO_REPLAY
+        sc = env._scene
+        for k in SCENE_KEYS_F64 + ("tgt_id", "uav_type"):
+            dst = sc[k]
+            if k == "uav_type" and not all("uav_type" in s for s in scenes):
+                continue
+            dt = np.int32 if dst.dtype == torch.int32 else np.float64
+            host = np.stack([np.asarray(s[k], dt).reshape(tuple(dst.shape[1:])) if np.size(s[k])
+                             else np.zeros(tuple(dst.shape[1:]), dt) for s in scenes])
+            dst.copy_(torch.from_numpy(host).to(env.device).repeat_interleave(K, dim=0))
+        env.istate.zero_()
+        env.score_pairs()
+        return S
+
+    def _generate_scenes(self, env, S, seed):
+        """S on-device Philox scenes (scene s = the generator's scene of env s under `seed`), each
+        with its pair tables repeated K times scene-major."""
+        K = self.K
+        env.desc.seed = int(seed) & (2 ** 64 - 1)
+        env.istate.zero_()
+        mask = torch.zeros(env.E, dtype=torch.uint8, device=env.device)
+        mask[:S] = 1
+        env.generate_scenes(mask)
+        if K > 1:
+            for t in env._scene.values():
+                t.copy_(t[:S].repeat_interleave(K, dim=0))
+        env.istate.zero_()
+
+    @torch.no_grad()
+    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False):
+        """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
+        `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
+        greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
+        the longest possible episode). Returns an Allocation."""
+        if (scenes is None) == (num_scenes is None):
+            raise ValueError("solve: pass scenes or num_scenes")
+        if isinstance(scenes, dict):
+            scenes = [scenes]
+        S = len(scenes) if scenes is not None else int(num_scenes)
+        if S <= 0:
+            raise ValueError("solve: no scenes")
+        seed = 0 if seed is None else int(seed)
+        K = self.K
+        with torch.cuda.device(self.device):
+            env = self._size(S)
+            if scenes is not None:
+                self._load_host_scenes(env, scenes)
+            else:
+                self._generate_scenes(env, S, seed)
+            n_max = int(self.N * self.M if max_steps is None else max_steps)
+            actions = torch.empty(n_max, env.E, dtype=torch.int8, device=env.device) if trace else None
+            self.steps.zero_()
+            self.ep_return.zero_()
+            env.reset(episode=1, obs_out=self.obs2[0])
+            self.policy.packed_weights()
+            self.policy.decode_steps(env, self.obs2, self.rowproj, 0, True, self.steps, self.finished, actions=actions,
+                                     ep_return=self.ep_return, n_max=n_max, greedy_stride=K, seed=seed, offset=0,
+                                     offset_stride=env.E)
+            best, J, covered, assignment = env.select_best(K)
+            replica_J = env.dstate[:, _lib.DST["J"]].reshape(S, K).clone()
+            steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
+        return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+
+
+def main(argv=None):
+    import argparse
+    import json
+    import time
+
+    from .checkpoint import load_checkpoint
+    from .policy import TransformerActorCritic
+    ap = argparse.ArgumentParser(description="Decode allocations for on-device scenes with a trained policy")
+    ap.add_argument("--checkpoint", required=True, help="a torch.save(policy.state_dict()) file (main_train.py:211)")
+    ap.add_argument("--scenes", type=int, default=1024)
+    ap.add_argument("--samples", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--uavs", type=int, default=default_cfg.NUM_UAVS)
+    ap.add_argument("--targets", type=int, default=default_cfg.NUM_TARGETS)
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("uavhip.solve decodes on the GPU (HIP) only")
+    dev = torch.device("cuda:0")
+    policy = TransformerActorCritic().to(dev)
+    load_checkpoint(policy, a.checkpoint)
+    solver = AllocationSolver(policy, a.uavs, a.targets, samples=a.samples)
+    solver.solve(num_scenes=a.scenes, seed=a.seed)  # warm-up: allocation, weight pack
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = solver.solve(num_scenes=a.scenes, seed=a.seed)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    r = r.cpu()
+    print(json.dumps({"scenes": a.scenes, "samples": a.samples, "N": a.uavs, "M": a.targets, "seed": a.seed,
+                      "mean_J": float(r.J.mean()), "best_J": float(r.J.max()),
+                      "mean_covered": float(r.covered.double().mean()), "mean_steps": float(r.steps.double().mean()),
+                      "unfinished": int((r.best_replica < 0).sum()), "scenes_per_s": a.scenes / dt}))
+
+
+if __name__ == "__main__":
+    main()

@@ -227,6 +227,26 @@ class VecUAVEnv:
         ids = torch.gather(self.tgt_id.long(), 1, a.clamp(min=0))
         return torch.where(a >= 0, ids, torch.full_like(ids, -1))
 
+    def select_best(self, K, best=None, J=None, covered=None, assignment=None):
+        """uavhip_select_best: the envs as K replicas of E / K scenes, scene-major (e = s * K + k).
+        Per scene the finished replica with the largest J (lowest k on a tie): (best [S] int32, -1
+        when none finished; J [S] f64; covered [S] int32; assignment [S, N] int32 target ids)."""
+        K = int(K)
+        if K <= 0 or self.E % K:
+            raise ValueError(f"select_best: K={K} must be > 0 and divide E={self.E}")
+        S, dev = self.E // K, self.device
+        best = torch.empty(S, dtype=torch.int32, device=dev) if best is None else best
+        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
+        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
+        assignment = torch.empty(S, self.N, dtype=torch.int32, device=dev) if assignment is None else assignment
+        check_out(best, "best", torch.int32, (S,), dev)
+        check_out(J, "J", torch.float64, (S,), dev)
+        check_out(covered, "covered", torch.int32, (S,), dev)
+        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
+        check(LIB.uavhip_select_best(self.desc, K, ptr(best), ptr(J), ptr(covered), ptr(assignment), stream_handle()),
+              "uavhip_select_best")
+        return best, J, covered, assignment
+
     def episodes(self):
         return self.istate[:, _lib.IST["EPISODE"]]
 
