@@ -363,6 +363,33 @@ int uavhip_rollout_steps(const uavhip_policy* policy, const uavhip_env* env, flo
                          float* value, int32_t auto_reset, double* reward, uint8_t* done, double* info,
                          uavhip_stream_t stream);
 
+/* uavhip_rollout_steps with the critic taken off the step chain, in two launches. Sampling and the
+ * env step read the actor's logits only, and the value of a window is read after the steps (GAE):
+ *  - uavhip_rollout_actor_steps: the n steps with the ACTOR trunk and head only. Arguments as
+ *    uavhip_rollout_steps without `value`; obs[t + 1], actions, logp, reward, done, info, the env
+ *    state and the actor's ring rows are bitwise uavhip_rollout_steps'. fill != 0 rebuilds the ring
+ *    rows of both trunks; after that the critic's ring rows are neither read nor written.
+ *  - uavhip_value_steps: the critic trunk and head alone over the recorded windows of one deque
+ *    sequence, obs [n + 1][B][5][14] f32 (the trajectory buffer after the steps): values [n][B] =
+ *    V(obs[t]), t < n, and last_values [B] = V(obs[n]) (nullable: obs[n] is then not read). `step`
+ *    is the ring step of obs[0]; it advances the critic's ring rows as the n (+ 1) steps of
+ *    uavhip_rollout_steps (+ uavhip_policy_value_rows) would. fill != 0 rebuilds the ring rows from
+ *    obs[0] first (not needed right after uavhip_rollout_actor_steps with fill on the same rowproj).
+ *    The windows are taken in groups of five consecutive steps: per window the critic runs up to
+ *    its last layer's attention, and that layer's out-projection, LayerNorms, FFN and the value
+ *    head run once per group on the five windows' last tokens together. stash: device scratch of
+ *    uavhip_value_steps_stash_floats(B) floats (contents unspecified before and after).
+ *    The values are bitwise those of uavhip_rollout_steps / uavhip_policy_value_rows. */
+int64_t uavhip_value_steps_stash_floats(int32_t B);
+int uavhip_rollout_actor_steps(const uavhip_policy* policy, const uavhip_env* env, float* obs, float* rowproj,
+                               int32_t step, int32_t n, int32_t fill, uint64_t seed, uint64_t offset,
+                               uint64_t offset_stride, const uint64_t* offset_dev, int8_t* actions, float* logp,
+                               int32_t auto_reset, double* reward, uint8_t* done, double* info,
+                               uavhip_stream_t stream);
+int uavhip_value_steps(const uavhip_policy* policy, const float* obs, int32_t B, int32_t n, float* rowproj,
+                       int32_t step, int32_t fill, float* values, float* last_values, float* stash,
+                       uavhip_stream_t stream);
+
 /* ---------------------------------------------------------------- inference (decode) */
 
 /* Decode an allocation with a trained policy: up to n_max steps of every env in ONE launch, each

@@ -38,7 +38,11 @@ x[: B // 4, :2] = 0
 a = torch.empty(B, dtype=torch.int8, device="cuda")
 lp = torch.empty(B, device="cuda")
 v = torch.empty(B, device="cuda")
-STEPS = os.environ.get("STEPS", "0") == "1"  # k_rollout_steps (one launch of 8 steps; last step's stamps)
+# VALUE=1: k_value_steps over the 10 windows (two full groups) a 9-step actor-only launch recorded; the
+# stamps are those of the last group: slots 0-4 and the C0 / C1 front slots of its last window, then
+# the group's batched tail (slots 5-7 and C1's tail slots)
+VALUE = os.environ.get("VALUE", "0") == "1"
+STEPS = os.environ.get("STEPS", "0") == "1" or VALUE  # k_rollout_steps (one launch of 8 steps; last step's stamps)
 fn = _lib.LIB.uavhip_steps_trace if STEPS else _lib.LIB.uavhip_policy_trace
 fn.restype = ctypes.c_int
 fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -53,7 +57,16 @@ if ENV:  # the stamps of the last of 8 fused steps
     eng.start()
     tr = eng.traj
     tr.obs[0].copy_(tr.obs[8])
-    if STEPS:
+    if VALUE:
+        NAMES.update({1: "v.x+mask", 2: "v.prologue", 3: "v.C1 front done", 4: "v.stash stored", 5: "v.group sync",
+                      6: "v.stash loaded", 7: "v.heads"})
+        big = RolloutEngine(env, net, horizon=9, deferred_value=False)
+        big.traj.obs[0].copy_(tr.obs[0])
+        tr = big.traj
+        net.rollout_actor_steps(env, tr.obs, big.rowproj, 0, True, tr.actions, tr.logp, tr.rewards, tr.dones, tr.info,
+                                seed=0, offset=0, offset_stride=B, offset_dev=big.counter)
+        net.value_steps(tr.obs, big.rowproj, 0, tr.values, tr.last_values)
+    elif STEPS:
         net.rollout_steps(env, tr.obs[:9].contiguous(), eng.rowproj, 0, True, tr.actions[:8], tr.logp[:8],
                           tr.values[:8], tr.rewards[:8], tr.dones[:8], tr.info[:8], seed=0, offset=0,
                           offset_stride=B, offset_dev=eng.counter)
@@ -81,6 +94,9 @@ if os.environ.get("WAVES") == "8":  # a TRACE_WAVES=8 build: [64 workgroups][8 w
     sys.exit(0)
 t = buf.reshape(256, 2, 64).astype(np.int64)
 slots = sorted((k for k in NAMES if (t[:, 0, k] != 0).all() and k not in ENVFINE), key=lambda k: np.median(t[:, 0, k] - t[:, 0, 0]))
+if VALUE:  # no sampling, no env step: the pass ends at slot 7
+    # (slots the actor launch stamped before the pass show as negative times: dropped)
+    slots = [k for k in slots if k < 60 and np.median(t[:, 0, k] - t[:, 0, 0]) >= 0]
 base = t[:, :, 0:1]
 rel = t - base
 print(f"B={B}; median cycles since block start (wave0 / wave4) and per-phase delta (wave0)")
@@ -97,8 +113,8 @@ if os.environ.get("ENVFINE") == "1":  # conditional stamps: only blocks whose st
         if ok.any():
             print(f"{k:3d} {ENVFINE[k]:18s} {int(np.median(t[ok, 0, k] - t[ok, 0, 61])):8d}  ({int(ok.sum())} blocks)")
 start = t[:, 0, 0]
-end = t[:, 0, 63 if ENV else 7]
-dur = (t[:, 0, 63 if ENV else 7] - t[:, 0, 0]).astype(np.float64)
+end = t[:, 0, 63 if ENV and not VALUE else 7]
+dur = (end - t[:, 0, 0]).astype(np.float64)
 q = np.percentile(dur, [0, 10, 50, 90, 99, 100])
 print("per-block duration (wave 0, cycles): min %d p10 %d median %d p90 %d p99 %d max %d; max/median %.3f"
       % (*q, q[5] / q[2]))

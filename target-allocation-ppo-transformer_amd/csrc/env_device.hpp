@@ -584,7 +584,10 @@ __device__ void write_info(const EnvRegs<TPL>& R, const uavhip_env& env, double 
 // auto_reset: 0 / nonzero as uavhip_env_step documents; HOLD instantiations (the decode kernel) also
 // take UAVHIP_STEP_HOLD: as 0, but stepping a finished env is no error -- it is held: R keeps every
 // value (R.err included), the outputs are a zero window, reward 0, done 1.
-template <int TPL, bool LT = false, bool HOLD = false>
+// TAG: unused -- an instantiation of its own for a second kernel of a translation unit, so that each
+// kernel keeps the only call of its instantiation (and with it the inlining and register allocation
+// it had: k_decode_steps' code object changed when k_rollout_actor_steps shared its instantiation).
+template <int TPL, bool LT = false, bool HOLD = false, int TAG = 0>
 __device__ void step_once(EnvRegs<TPL>& R, const uavhip_env& env, int e, int lane, int a, int auto_reset,
                           float* obs_o, double* rew_o, uint8_t* done_o, double* info_o) {
     const int N = env.N, M = env.M;

@@ -433,8 +433,8 @@ __device__ void gstore_delta(const GRegs& R, const uavhip_env& env, int e, int j
     if (j < kObs - 2 * L) w[2 * L + j] = R.w2;
 }
 
-// One UAVEnv.step (uav_env.py:295-435) of this group's env (envdev::step_once; HOLD as there).
-template <bool TAB = true, bool HOLD = false>
+// One UAVEnv.step (uav_env.py:295-435) of this group's env (envdev::step_once; HOLD and TAG as there).
+template <bool TAB = true, bool HOLD = false, int TAG = 0>
 __device__ void gstep(GRegs& R, const uavhip_env& env, int e, int j, int a, int auto_reset, float* obs_o,
                       double* rew_o, uint8_t* done_o, double* info_o) {
     const int N = env.N, M = env.M;

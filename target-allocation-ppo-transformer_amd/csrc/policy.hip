@@ -1051,10 +1051,13 @@ __device__ __forceinline__ float in_inv(const Smem& sm, int tok) {
 // [qt, qt + 16) (column tile qt / 16, [b * 5 + s] rows), its residual in sm.h, LN2's output as planes
 // for the kernel's next in_proj (ps_inproj); and K7's pruned layers take their residual from sm.h
 // (PSX = 2).
-template <int trunk, int layer, bool last, bool TR = false, class F = NoHook, int PSX = 0>
+// BATCH (k_value_steps): the full-width tail (80 tokens) of a layer whose in_proj ran pruned -- the
+// tokens are the last positions of five consecutive windows, tile w = window w, their attention
+// output's planes in sm.ctx and each lane's own residual elements in registers (`bres`, one per tile).
+template <int trunk, int layer, bool last, bool TR = false, class F = NoHook, int PSX = 0, bool BATCH = false>
 __device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restrict__ P, const TailPre<last, TR, PSX>& po,
                                            const TrainLayerIO& io = TrainLayerIO{}, int b0 = 0, F pre_ln2 = F{},
-                                           int qt = 0) {
+                                           int qt = 0, [[maybe_unused]] const f32x4* bres = nullptr) {
     constexpr int DP = tail_depth<last, TR, PSX>();
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
     constexpr int CT = (last || PSX) ? 1 : S;
@@ -1068,7 +1071,8 @@ __device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restri
     // full forward's pruned next layer)
     constexpr bool next_planes = !last && split_inproj<trunk, layer + 1>();
     constexpr bool row4 = next_planes && !PSX;
-    constexpr bool res_ctx = split_inproj<trunk, layer>() && !PSX;  // the residual is in sm.ctx rows 0-15
+    constexpr bool res_ctx = split_inproj<trunk, layer>() && !PSX && !BATCH;  // the residual is in sm.ctx rows 0-15
+    static_assert(!BATCH || (!last && !TR && !PSX && !next_planes), "the value pass's batched tail");
     static_assert(!res_ctx || last, "a split in_proj feeds a pruned layer");
     constexpr bool kC0 = trunk != 0 && layer == 0 && !TR && !PSX;  // trace stamps of the critic's layer-0 LNs
     const int wv = TIDX() >> 6;
@@ -1110,7 +1114,7 @@ __device__ __forceinline__ void layer_tail(TID_F Smem& sm, const float* __restri
             residual_layernorm<CT, TR, true>(TID_C sm, acc, lp, t0, lo1, h1, r4, s_ln1.sc);
         } else {
             residual_layernorm<CT, TR, true, false, kC0 ? 55 : -1, kC0 ? 56 : -1, kC0 ? 57 : -1>(TID_C sm, acc, lp, t0, lo1, h1,
-                                                                                            nullptr, s_ln1.sc);
+                                                                                            BATCH ? bres : nullptr, s_ln1.sc);
         }
     }
     PTR(tb + 8);
@@ -1185,7 +1189,9 @@ __device__ __forceinline__ void layer_tail_fwd(TID_F Smem& sm, const float* __re
 //   layer 0 (training forward): in sm.ctx (the embedding wrote them beside its fp32 rows in sm.h) --
 //               so chunk 0's attention output waits in registers until chunk 1's GEMMs have read
 //               sm.ctx, then both chunks are written.
-template <int trunk, int layer, bool last, bool TR, class F = NoHook>
+// TAIL = false (k_value_steps): stops after the attention -- its output's planes in sm.ctx rows 64-79
+// and the residual rows still in sm.ctx rows 0-15; the caller runs the tail later (layer_tail BATCH).
+template <int trunk, int layer, bool last, bool TR, class F = NoHook, bool TAIL = true>
 __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float* __restrict__ P, HPre<2> pkv,
                                                     const TrainLayerIO& io, int b0, F pre_ln2) {
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
@@ -1230,7 +1236,7 @@ __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float*
                     (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, qtok0 + 16 * ct + i16) + bq;
         }
         if (c == 0) pkv = hprefetch<2>(TID_C P, si, D, kv_row(wv, 1), 0);
-        else po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
+        else if constexpr (TAIL) po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
         PTR(tb + 1 + 3 * c);
         __syncthreads();
         PTR(tb + 2 + 3 * c);
@@ -1264,7 +1270,7 @@ __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float*
         __syncthreads();
         PTR(tb + 3 + 3 * c);
     }
-    layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
+    if constexpr (TAIL) layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
 }
 
 // One post-LN nn.TransformerEncoderLayer (relu FFN 256, 8 heads). last: prune to column tile 4.
@@ -1584,7 +1590,8 @@ __device__ __forceinline__ void rows_prologue(TID_F Smem& sm, const float* __res
 }
 
 // 128 -> 64 (MFMA, waves 0-3) -> relu -> nout (VALU) on the last-position rows (transformer_net.py:77-91)
-template <int head, int nout, int DQ = 4>
+// (XT: the rows' first token in sm.h; k_value_steps' batched tail has five tiles of them)
+template <int head, int nout, int DQ = 4, int XT = (S - 1) * SPW>
 __device__ void head_mlp(TID_F Smem& sm, const float* __restrict__ P, const APre<DQ>& pw, float* out) {
     const float* W0 = P + kOffs.o[head + 0];
     const float* b0 = P + kOffs.o[head + 1];
@@ -1598,7 +1605,7 @@ __device__ void head_mlp(TID_F Smem& sm, const float* __restrict__ P, const APre
     const int p = item / nout, a = (item - p * nout) % nout;  // in range for every thread
     const f32x4 w2 = *reinterpret_cast<const f32x4*>(W2 + a * HID + 4 * k4);
     const float bb2 = b2[a];
-    if (wv < HID / 16) linear1<1, true, DQ>(TID_C pw, W0, D, b0, 16 * wv, sm.h, LDH, (S - 1) * SPW, sm.z, LDZ, 16 * wv, 0);
+    if (wv < HID / 16) linear1<1, true, DQ>(TID_C pw, W0, D, b0, 16 * wv, sm.h, LDH, XT, sm.z, LDZ, 16 * wv, 0);
     __syncthreads();
     if (item < kItems) {  // wave-uniform: kItems * 16 is a multiple of 64
         const f32x4 z = *reinterpret_cast<const f32x4*>(sm.z + p * LDZ + 4 * k4);
@@ -1841,7 +1848,8 @@ enum { kEnvGrp = 1, kEnvWave = 2, kEnvBoth = 3 };
 // AONLY (inference, ROWS, ENV): the mirror image, the actor trunk and head only and then the env step
 // (k_decode_steps) -- the critic's ring rows are neither read nor written, no value; env b decodes
 // greedily (a = l1 > l0) iff greedy_stride > 0 and b % greedy_stride == 0, else it samples.
-template <bool TR, bool ROWS, int ENV, bool VONLY = false, bool AONLY = false>
+// ETAG: the env step's instantiation tag (envdev::step_once TAG; 1 in k_rollout_actor_steps).
+template <bool TR, bool ROWS, int ENV, bool VONLY = false, bool AONLY = false, int ETAG = 0>
 __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __restrict__ P, const float* __restrict__ states,
                                              int B, const int8_t* __restrict__ actions_in, uint64_t seed,
                                              uint64_t offset, const uint64_t* __restrict__ offset_dev,
@@ -2122,7 +2130,7 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
             R.win = sm.h + (2 * wve + g) * envgrp::kWin;
             envgrp::gload_finish(R, gq, env, e, j);
             PTR(61);
-            envgrp::gstep<false, AONLY>(R, env, e, j, sm.mask[2 * wve + g], eo.auto_reset, obs_at(eo.obs, e, obs_f16(env)),
+            envgrp::gstep<false, AONLY, ETAG>(R, env, e, j, sm.mask[2 * wve + g], eo.auto_reset, obs_at(eo.obs, e, obs_f16(env)),
                           (AONLY && !eo.rew) ? nullptr : eo.rew + e,  // the decode's return is optional
                           eo.done + e, eo.info ? eo.info + (size_t)e * UAVHIP_INFO_COUNT : nullptr);
             PTR(62);
@@ -2141,7 +2149,7 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
                 if (k == 1 && !two) break;
                 EnvRegs<1>& R = k ? R1 : R0;
                 const int e = e0 + k;
-                step_once<1, false, AONLY>(R, env, e, lane, sm.mask[2 * wve + k], eo.auto_reset,
+                step_once<1, false, AONLY, ETAG>(R, env, e, lane, sm.mask[2 * wve + k], eo.auto_reset,
                                     obs_at(eo.obs, e, obs_f16(env)), (AONLY && !eo.rew) ? nullptr : eo.rew + e,
                                     eo.done + e,
                                     eo.info ? eo.info + (size_t)e * UAVHIP_INFO_COUNT : nullptr);
@@ -2203,6 +2211,23 @@ struct DecodeArgs {
     double* ep_return;     // [B] (nullable); between the steps the env step's reward
 };
 int launch_decode_steps(const DecodeArgs& da, hipStream_t stream);
+// k_rollout_actor_steps (uavhip_rollout_actor_steps): k_rollout_steps' arguments without the value
+int launch_rollout_actor_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
+                               const uint64_t* offset_dev, int8_t* actions, float* logp, const RowIO& rio,
+                               const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream);
+// k_value_steps' only parameter (uavhip_value_steps; the same translation unit as k_rollout_steps)
+struct ValueArgs {
+    const float* P;
+    const float* obs;      // [n + 1][B][5][14]: the recorded windows of one deque sequence
+    int B, n;              // windows per step; steps with a value row
+    long long obs_stride;  // floats from obs[t] to obs[t + 1]
+    RowIO rio;             // ring step of obs[0]
+    float* values;         // [n][B]
+    float* last_values;    // [B]: V of obs[n] (nullable: the pass stops at obs[n - 1])
+    float* stash;          // [ceil(B / 16)][5][2 * 16 * 136]: the groups' attention outputs and residual rows
+};
+int launch_value_steps(const ValueArgs& va, hipStream_t stream);
+constexpr int kVG = S;  // k_value_steps: windows per group, one 16-token tile each
 #ifdef UAVHIP_STEPS_TU
 // All of the launch's arguments in one struct: the kernel's only parameter, so the kernarg
 // segment holds exactly this struct at offset 0.
@@ -2369,6 +2394,191 @@ int launch_decode_steps(const DecodeArgs& da, hipStream_t stream) {
     else
         hipLaunchKernelGGL(k_decode_steps<kEnvWave>, dim3((da.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, da);
     return check_launch("k_decode_steps");
+}
+
+// Rollout with the critic taken off the step chain (uavhip_rollout_actor_steps + uavhip_value_steps).
+// Sampling and the env step read the actor's logits only; the value of a window is read by the GAE
+// alone, after the launch. k_rollout_actor_steps is k_rollout_steps' loop over the actor-only block
+// (policy_block AONLY, as k_decode_steps but with the rollout's auto-reset, sampling for every env
+// and the trajectory outputs): every window, action, logp, reward, done, info row, the env state and
+// the actor's ring rows are bitwise k_rollout_steps'; no value is written and the critic's ring rows
+// are not touched. k_value_steps then walks the recorded windows obs[0 .. n] with the critic alone, on
+// the critic's ring rows (below): the values are bitwise k_rollout_steps'.
+template <int ENVP>
+__global__ __launch_bounds__(NTHR) void k_rollout_actor_steps(const StepsArgs args) {
+    __shared__ __attribute__((aligned(16))) Smem sm;
+    if (threadIdx.x >= NTHR / 2) __builtin_amdgcn_s_setprio(1);
+    if (threadIdx.x == 0) g_tid_zero = 0;
+    load_rtab(TID_K sm, args.P);
+    for (int t = 0; t < args.seq.n; ++t) {
+        __syncthreads();  // g_tid_zero; the previous step's LDS scratch and global stores
+        typedef const __attribute__((address_space(4))) StepsArgs* kargs;
+        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+        int bx = blockIdx.x;
+        unsigned tid = threadIdx.x;
+        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
+        tid &= NTHR - 1;
+        const StepsArgs& a = *(const StepsArgs*)ka;
+        const size_t o = (size_t)t * a.B;
+        const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
+        const EnvOut e{a.eo.auto_reset, a.eo.obs + t * a.seq.obs_stride, a.eo.rew + o, a.eo.done + o,
+                       a.eo.info ? a.eo.info + o * UAVHIP_INFO_COUNT : nullptr};
+        policy_block<false, true, ENVP, false, true, 1>(tid, sm, a.P, a.states + t * a.seq.obs_stride, a.B, nullptr,
+                                                     a.seed, a.offset + t * a.seq.off_stride, a.offset_dev,
+                                                     a.action_out + o, a.logp_out + o, nullptr, nullptr, nullptr,
+                                                     TrainIO{}, r, a.env, e, bx, 0);
+    }
+}
+int launch_rollout_actor_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
+                               const uint64_t* offset_dev, int8_t* actions, float* logp, const RowIO& rio,
+                               const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream) {
+    // one env path per instantiation, chosen as launch_rollout_steps chooses
+    const StepsArgs sa{P, obs, B, seed, offset, offset_dev, actions, logp, nullptr, rio, env, eo, seq};
+    if (env.N <= envgrp::L && env.M <= envgrp::L && B % 2 == 0)
+        hipLaunchKernelGGL(k_rollout_actor_steps<kEnvGrp>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
+    else
+        hipLaunchKernelGGL(k_rollout_actor_steps<kEnvWave>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
+    return check_launch("k_rollout_actor_steps");
+}
+
+// k_value_steps: the windows in groups of kVG consecutive steps (the last group may be shorter). Per
+// window, value_front runs the critic up to layer 1's attention exactly as the value-only block
+// does -- layer 0 on the ring rows, layer 1's K | V GEMM, the last token's attention -- and stashes
+// the 16 attention-output rows (their fp16 planes) and the 16 residual rows (fp32) of the window in
+// the workgroup's slice of `stash` (LDS is full; the slice, 85 KB, stays in the L2). Layer 1's
+// out-projection, LN1, FFN1, FFN2, LN2 and the value head, which the per-step kernels run on one
+// 16-token tile per step with every weight streamed from the L2 for it, then run once per group on
+// the kVG x 16 stashed tokens as full 80-token tiles (layer_tail BATCH: tile w = window w). Every
+// token's sums are formed in the per-step order, so the values are bitwise k_rollout_steps'.
+// No workgroup reads what another wrote; every barrier is in workgroup-uniform control flow (the
+// group sizes derive from the kernel's arguments alone).
+constexpr int kStashVec = 2 * SPW * LDH / 4;  // float4s per window: planes rows, then residual rows
+static_assert(LDP * 2 == LDH * 4, "a planes row and an fp32 row are the same bytes");
+__device__ __forceinline__ void value_front(TID_F Smem& sm, const float* __restrict__ P, const float* __restrict__ states,
+                                            int B, const RowIO& rio, int b0, f32x4* __restrict__ st) {
+    PTR(0);
+    gather_windows<false, true>(TID_C sm, states, B, TrainIO{}, b0, false, P + kRangeOff);
+    __syncthreads();
+    PTR(1);
+    a0f_from_tmax(TID_C sm);
+    {
+        RingPre<kCriticTrunk> pw[3];
+        RowPre<3> rp;
+        rows_prologue<kCriticTrunk>(TID_C sm, P, pw, rp, rio, b0);
+        PTR(2);
+        __syncthreads();
+        encoder_layer_rows<kCriticTrunk>(TID_C sm, P, pw, rp, rio, b0);
+    }
+    const KvPre<kCriticTrunk, 1, false> pkv = kv_prefetch<kCriticTrunk, 1, false>(TID_C P);
+    __syncthreads();
+    encoder_layer_split<kCriticTrunk, 1, true, false, NoHook, false>(TID_C sm, P, pkv, TrainLayerIO{}, b0, NoHook{});
+    // the attention output's planes (sm.ctx rows 64-79) and the residual rows (sm.ctx rows 0-15, fp32)
+    PTR(3);
+    const f32x4* cx = reinterpret_cast<const f32x4*>(sm.ctx);
+    for (int i = TIDX(); i < kStashVec; i += NTHR) {
+        const int h = kStashVec / 2;
+        st[i] = i < h ? cx[(S - 1) * SPW * LDH / 4 + i] : cx[i - h];
+    }
+    PTR(4);
+}
+// The value head's first layer (128 -> 64, ReLU) on the batched tail's 80 tokens: sm.h -> z rows in
+// sm.big (free after FFN2), feature tile wv & 3 of CT token tiles from tok0 (waves 0-3: tiles 0-2,
+// waves 4-7: tiles 3-4, so both waves of a SIMD work). Per token the sums are head_mlp's.
+template <int CT>
+__device__ __forceinline__ void value_head_gemm(TID_F Smem& sm, const float* __restrict__ P, const APre<KB>& pw, int tok0) {
+    const int row = 16 * ((TIDX() >> 6) & 3);
+    linear1<CT, true, KB>(TID_C pw, P + kOffs.o[kCriticHead + 0], D, P + kOffs.o[kCriticHead + 1], row, sm.h, LDH, tok0,
+                         sm.big, LDZ, row, tok0);
+}
+__global__ __launch_bounds__(NTHR) void k_value_steps(const ValueArgs args) {
+    __shared__ __attribute__((aligned(16))) Smem sm;
+    if (threadIdx.x >= NTHR / 2) __builtin_amdgcn_s_setprio(1);
+    if (threadIdx.x == 0) g_tid_zero = 0;
+    load_rtab(TID_K sm, args.P);
+    const int nt = args.n + (args.last_values ? 1 : 0);  // workgroup-uniform (kernel arguments)
+    for (int t0 = 0; t0 < nt; t0 += kVG) {
+        for (int w = 0; w < kVG && t0 + w < nt; ++w) {
+            __syncthreads();  // g_tid_zero; the previous window's LDS reads and ring-row stores
+            typedef const __attribute__((address_space(4))) ValueArgs* kargs;
+            kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+            int bx = blockIdx.x;
+            unsigned tid = threadIdx.x;
+            asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
+            tid &= NTHR - 1;
+            const ValueArgs& a = *(const ValueArgs*)ka;
+            const int t = t0 + w;
+            const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
+            value_front(tid, sm, a.P, a.obs + t * a.obs_stride, a.B, r, bx * SPW,
+                        reinterpret_cast<f32x4*>(a.stash) + ((size_t)bx * kVG + w) * kStashVec);
+        }
+        __syncthreads();  // the stash stores (read back by other lanes); sm.ctx is rewritten
+        typedef const __attribute__((address_space(4))) ValueArgs* kargs;
+        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
+        int bx = blockIdx.x;
+        unsigned tid = threadIdx.x;
+        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
+        tid &= NTHR - 1;
+        const ValueArgs& a = *(const ValueArgs*)ka;
+        const int gw = min(kVG, nt - t0), b0 = bx * SPW;
+        PTR(5);
+        // tile w <- window w: the planes to sm.ctx (every load issued before the first LDS store;
+        // unconditional, clamped loads), each lane's own residual elements to registers -- their round
+        // trip hides under the out-projection. The plane tiles of a short group are zero; their residual
+        // is whatever the stash holds (tokens are independent and those tiles' values are not written).
+        f32x4 res[kVG];
+        {
+            const f32x4* st = reinterpret_cast<const f32x4*>(a.stash) + (size_t)bx * kVG * kStashVec;
+            constexpr int h = kStashVec / 2, kAll = kVG * h, kIt = (kAll + NTHR - 1) / NTHR;
+            f32x4* cx = reinterpret_cast<f32x4*>(sm.ctx);
+            f32x4 v[kIt];
+#pragma unroll
+            for (int u = 0; u < kIt; ++u) {
+                const int i = min((int)tid + u * NTHR, kAll - 1), w = i / h;
+                v[u] = st[w * kStashVec + (i - w * h)];
+            }
+            const int ro = h + (tid & 15) * (LDH / 4) + 4 * (tid >> 6) + ((tid >> 4) & 3);
+#pragma unroll
+            for (int w = 0; w < kVG; ++w) res[w] = st[w * kStashVec + ro];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < kIt; ++u) {
+                const int i = tid + u * NTHR;
+                if (i < kAll) cx[i] = i / h < gw ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        const TailPre<false, false> po = tail_prefetch<kCriticTrunk, 1, false, false>(tid, a.P);
+        PTR(6);
+        __syncthreads();
+        layer_tail<kCriticTrunk, 1, false, false, NoHook, 0, true>(tid, sm, a.P, po, TrainLayerIO{}, b0, NoHook{}, 0, res);
+        // the value head on the 80 tokens: first layer on the MFMA, second on the VALU (16 lanes per
+        // token, head_mlp's sums), its operands loaded ahead of the barriers
+        const int wv = tid >> 6, k4 = tid & 15;
+        const APre<KB> ph = prefetch<KB>(tid, a.P + kOffs.o[kCriticHead + 0], D, 16 * (wv & 3), 0);  // the whole tile
+        const f32x4 w2 = *reinterpret_cast<const f32x4*>(a.P + kOffs.o[kCriticHead + 2] + 4 * k4);
+        const float bb2 = a.P[kOffs.o[kCriticHead + 3]];
+        __syncthreads();
+        if (wv < 4) value_head_gemm<3>(tid, sm, a.P, ph, 0);
+        else value_head_gemm<2>(tid, sm, a.P, ph, 3 * SPW);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < (TOK * 16 + NTHR - 1) / NTHR; ++r) {
+            const int tok = (NTHR / 16) * r + (tid >> 4);
+            if (tok < TOK) {  // wave-uniform
+                const f32x4 z = *reinterpret_cast<const f32x4*>(sm.big + tok * LDZ + 4 * k4);
+                float acc = (w2.x * z.x + w2.y * z.y) + (w2.z * z.z + w2.w * z.w);
+                acc = add_xor2(add_xor1(acc));
+                acc += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc), 0x141, 0xF, 0xF, true));  // row_half_mirror
+                acc += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc), 0x140, 0xF, 0xF, true));  // row_mirror
+                const int w = tok / SPW, b = b0 + (tok & (SPW - 1)), t = t0 + w;
+                if (k4 == 0 && w < gw && b < a.B) (t < a.n ? a.values + (size_t)t * a.B : a.last_values)[b] = acc + bb2;
+            }
+        }
+        PTR(7);
+    }
+}
+int launch_value_steps(const ValueArgs& va, hipStream_t stream) {
+    hipLaunchKernelGGL(k_value_steps, dim3((va.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, va);
+    return check_launch("k_value_steps");
 }
 #endif  // UAVHIP_STEPS_TU
 
@@ -4082,6 +4292,65 @@ extern "C" int uavhip_rollout_steps(const uavhip_policy* policy, const uavhip_en
     return pol::launch_rollout_steps(policy->weights, obs, (int)B, seed, offset, offset_dev, actions, logp, value, rio,
                                      *env, pol::EnvOut{(int)auto_reset, obs + stride, reward, done, info},
                                      pol::StepSeq{(int)n, stride, offset_stride}, (hipStream_t)stream);
+}
+
+// uavhip_rollout_steps without the critic (k_rollout_actor_steps); uavhip_value_steps supplies the values.
+extern "C" int uavhip_rollout_actor_steps(const uavhip_policy* policy, const uavhip_env* env, float* obs,
+                                          float* rowproj, int32_t step, int32_t n, int32_t fill, uint64_t seed,
+                                          uint64_t offset, uint64_t offset_stride, const uint64_t* offset_dev,
+                                          int8_t* actions, float* logp, int32_t auto_reset, double* reward,
+                                          uint8_t* done, double* info, uavhip_stream_t stream) {
+    if (const int rc = validate_env(env, true)) return rc;
+    const int32_t B = env->E;
+    if (const int rc = check_policy("uavhip_rollout_actor_steps", policy, obs, B)) return rc;
+    if (env->N > 64 || env->M > 64 || (env->flags & UAVHIP_ENV_OBS_F16) || !actions || !logp || !reward || !done ||
+        n <= 0) {
+        set_error("uavhip_rollout_actor_steps: N=%d, M=%d must be <= 64, observations f32, n=%d > 0 and "
+                  "actions/logp/reward/done non-NULL", env->N, env->M, n);
+        return UAVHIP_EINVAL;
+    }
+    if (!rowproj || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
+        set_error("uavhip_rollout_actor_steps: NULL rowproj, step=%d < 0 or E=%d above the ring's 32-bit offsets", step,
+                  B);
+        return UAVHIP_EINVAL;
+    }
+    const int grid = (B + pol::SPW - 1) / pol::SPW;
+    const pol::RowIO rio{rowproj, (int)B, (int)step};
+    if (fill) {
+        hipLaunchKernelGGL(pol::k_policy_rows_fill, dim3(grid > pol::kPposParts ? grid : pol::kPposParts), dim3(pol::NTHR), 0,
+                           (hipStream_t)stream, policy->weights, obs, rio);
+        if (const int rc = check_launch("k_policy_rows_fill")) return rc;
+    }
+    const long long stride = (long long)B * pol::S * pol::IN;
+    return pol::launch_rollout_actor_steps(policy->weights, obs, (int)B, seed, offset, offset_dev, actions, logp, rio,
+                                           *env, pol::EnvOut{(int)auto_reset, obs + stride, reward, done, info},
+                                           pol::StepSeq{(int)n, stride, offset_stride}, (hipStream_t)stream);
+}
+
+// The values of the recorded windows obs[0 .. n - 1] (and of obs[n] when last_values is given) on the
+// critic's ring rows, one launch (k_value_steps).
+extern "C" int64_t uavhip_value_steps_stash_floats(int32_t B) {
+    return B > 0 ? (int64_t)((B + pol::SPW - 1) / pol::SPW) * pol::kVG * 2 * pol::SPW * (pol::D + 8) : -1;
+}
+extern "C" int uavhip_value_steps(const uavhip_policy* policy, const float* obs, int32_t B, int32_t n, float* rowproj,
+                                  int32_t step, int32_t fill, float* values, float* last_values, float* stash,
+                                  uavhip_stream_t stream) {
+    if (const int rc = check_policy("uavhip_value_steps", policy, obs, B)) return rc;
+    if (!rowproj || !values || !stash || n <= 0 || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
+        set_error("uavhip_value_steps: NULL rowproj / values / stash, n=%d <= 0, step=%d < 0 or B=%d above the ring's 32-bit "
+                  "offsets", n, step, B);
+        return UAVHIP_EINVAL;
+    }
+    const int grid = (B + pol::SPW - 1) / pol::SPW;
+    const pol::RowIO rio{rowproj, (int)B, (int)step};
+    if (fill) {
+        hipLaunchKernelGGL(pol::k_policy_rows_fill, dim3(grid > pol::kPposParts ? grid : pol::kPposParts), dim3(pol::NTHR), 0,
+                           (hipStream_t)stream, policy->weights, obs, rio);
+        if (const int rc = check_launch("k_policy_rows_fill")) return rc;
+    }
+    return pol::launch_value_steps(pol::ValueArgs{policy->weights, obs, (int)B, (int)n, (long long)B * pol::S * pol::IN,
+                                                  rio, values, last_values, stash},
+                                   (hipStream_t)stream);
 }
 
 // Inference: up to n_max actor-only steps of every env in one launch (k_decode_steps).

@@ -104,6 +104,12 @@ _SIGS = {
     "uavhip_rollout_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), _vp, _vp, _i32,
                                             _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
                                             _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "uavhip_rollout_actor_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), _vp, _vp, _i32,
+                                                  _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp,
+                                                  _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "uavhip_value_steps_stash_floats": (ctypes.c_int64, [_i32]),
+    "uavhip_value_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp,
+                                          _vp, _vp]),
     "uavhip_decode_steps": (ctypes.c_int, [ctypes.POINTER(PolicyDesc), ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _i32,
                                            _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
                                            _vp, _vp, _vp, _vp]),

@@ -77,6 +77,7 @@ class TransformerActorCritic(nn.Module):
         self._packed = None
         self._packed_key = None
         self._desc = None
+        self._value_stash = {}  # value_steps' kernel scratch per (B, device)
         # Philox key of the on-device action sampling: torch.initial_seed() (so torch.manual_seed
         # controls it, as it controls the reference's Categorical sampling, transformer_net.py:120)
         # mixed with a per-process instance count (separate instances sample independently). Nothing
@@ -92,6 +93,7 @@ class TransformerActorCritic(nn.Module):
         # the packed-weight cache and its ctypes descriptor are per-instance device state
         state = self.__dict__.copy()
         state["_packed"] = state["_packed_key"] = state["_desc"] = None
+        state["_value_stash"] = {}
         return state
 
     # ------------------------------------------------------------------ torch path
@@ -256,6 +258,60 @@ class TransformerActorCritic(nn.Module):
                                        ctypes.c_uint64(offset_stride), ptr(offset_dev), ptr(actions), ptr(logp),
                                        ptr(value), int(bool(auto_reset)), ptr(rewards), ptr(dones), ptr(info),
                                        stream_handle()), "uavhip_rollout_steps")
+
+    def rollout_actor_steps(self, env, obs, rowproj, step, fill, actions, logp, rewards, dones, info=None,
+                            auto_reset=True, seed=None, offset=0, offset_stride=0, offset_dev=None):
+        """uavhip_rollout_actor_steps: rollout_steps() without the critic -- the same windows, actions,
+        logp, rewards, dones, info, env state and actor ring rows, bitwise, and no value (value_steps()
+        computes the values from the recorded windows afterwards)."""
+        if self._packed is None:
+            self.packed_weights()
+        E, dev = env.E, env.device
+        n = actions.shape[0] if actions.dim() == 2 else -1
+        if n <= 0:
+            raise ValueError("actions: need an int8 [n][E] buffer with n > 0")
+        check_out(obs, "obs", torch.float32, (n + 1, E), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
+        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or rowproj.dtype != torch.float32 or \
+                not rowproj.is_contiguous():
+            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
+        for t, name, dt, tail in ((actions, "actions", torch.int8, ()), (logp, "logp", torch.float32, ()),
+                                  (rewards, "rewards", torch.float64, ()), (dones, "dones", torch.uint8, ()),
+                                  (info, "info", torch.float64, (_lib.INFO_COUNT,))):
+            check_out(t, name, dt, (n, E), dev, tail)
+        seed = self.sample_seed if seed is None else seed
+        check(LIB.uavhip_rollout_actor_steps(self._desc, env.desc, ptr(obs), ptr(rowproj), int(step), int(n),
+                                             int(bool(fill)), ctypes.c_uint64(seed), ctypes.c_uint64(offset),
+                                             ctypes.c_uint64(offset_stride), ptr(offset_dev), ptr(actions),
+                                             ptr(logp), int(bool(auto_reset)), ptr(rewards), ptr(dones), ptr(info),
+                                             stream_handle()), "uavhip_rollout_actor_steps")
+
+    def value_steps(self, obs, rowproj, step, values, last_values=None, fill=False):
+        """uavhip_value_steps: the critic's values of the recorded windows of one deque sequence, obs
+        [n + 1][B][5][14] f32, in one launch: values [n][B] = V(obs[t]) and, if given, last_values [B] =
+        V(obs[n]). Bitwise the values rollout_steps() / value_rows() write. step: the ring step of
+        obs[0]; fill=True rebuilds the ring rows from obs[0] first. The kernel's scratch
+        (uavhip_value_steps_stash_floats(B) floats) is allocated on first use and kept per (B, device)."""
+        if self._packed is None:
+            self.packed_weights()
+        n = values.shape[0] if values.dim() == 2 else -1
+        if n <= 0:
+            raise ValueError("values: need a float32 [n][B] buffer with n > 0")
+        B, dev = values.shape[1], obs.device
+        check_out(obs, "obs", torch.float32, (n + 1, B), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
+        check_out(values, "values", torch.float32, (n, B), dev)
+        check_out(last_values, "last_values", torch.float32, (B,), dev)
+        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(B) or rowproj.dtype != torch.float32 or \
+                not rowproj.is_contiguous():
+            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(B)")
+        key = (B, str(dev))
+        stash = self._value_stash.get(key)
+        if stash is None:
+            stash = self._value_stash[key] = torch.empty(LIB.uavhip_value_steps_stash_floats(B), dtype=torch.float32,
+                                                         device=dev)
+        check(LIB.uavhip_value_steps(self._desc, ptr(obs), B, int(n), ptr(rowproj), int(step), int(bool(fill)),
+                                     ptr(values), ptr(last_values), ptr(stash), stream_handle()),
+              "uavhip_value_steps")
+        return values
 
     def decode_steps(self, env, obs2, rowproj, step, fill, steps, finished, actions=None, ep_return=None,
                      n_max=None, greedy_stride=1, seed=None, offset=0, offset_stride=0, offset_dev=None):

@@ -26,6 +26,9 @@ from .ppo import gae, gae_workspace
 # UAVHIP_BOOTSTRAP_FULL=1: the bootstrap V(s_T) through the full forward (actor + sampling + critic)
 # instead of the critic-only launch -- the same values, bitwise (A/B switch of scripts/gpu_r04z.sh)
 _BOOTSTRAP_FULL = os.environ.get("UAVHIP_BOOTSTRAP_FULL", "0") == "1"
+# RolloutEngine(deferred_value=None): whether an engine built with default arguments takes the critic
+# off the step chain (DESIGN.md 10 has the measurements behind the setting)
+DEFERRED_VALUE_DEFAULT = True
 
 
 class Trajectory:
@@ -47,7 +50,7 @@ class Trajectory:
 
 class RolloutEngine:
     def __init__(self, env, policy, horizon, want_info=True, bootstrap=True, seed=None, normalize=True, row_cache=True,
-                 fused_step=None, total_envs=None, persistent=None, group=None):
+                 fused_step=None, total_envs=None, persistent=None, group=None, deferred_value=None):
         """normalize=False leaves the advantages raw after GAE: a data-parallel caller normalises
         them with the moments of the whole data-parallel batch in normalize_global() (called by
         gather()) (ppo.py:94).
@@ -57,6 +60,12 @@ class RolloutEngine:
         persistent: the T fused steps of an iteration as ONE launch (uavhip_rollout_steps: every
         workgroup loops over the steps of its own envs); default on with fused_step and f32
         observations. Bitwise the same trajectory as T uavhip_rollout_step launches.
+        deferred_value: the persistent iteration as two launches -- the T steps with the actor alone
+        (uavhip_rollout_actor_steps), then the critic over the recorded windows, bootstrap included
+        (uavhip_value_steps) -- instead of uavhip_rollout_steps + uavhip_policy_value_rows. The
+        trajectory, the env state and the values are bitwise the same. Needs the persistent path;
+        default DEFERRED_VALUE_DEFAULT when the caller left fused_step and persistent at None (an
+        explicit persistent=True always runs uavhip_rollout_steps).
         seed: Philox key of the action sampling (default: the policy's sample_seed, drawn from
         torch's RNG). Sampling counters are global env indices: step t of env e draws counter
         t * total_envs + env.env_base + e, so a rank's shard (VecUAVEnv(env_base=shard start),
@@ -95,6 +104,10 @@ class RolloutEngine:
         if persistent and not can_persist:
             raise ValueError("persistent needs fused_step and float32 observations")
         self.persistent = can_persist if persistent is None else bool(persistent)
+        if deferred_value and not self.persistent:
+            raise ValueError("deferred_value needs the persistent rollout (fused_step, float32 observations)")
+        self.deferred_value = (DEFERRED_VALUE_DEFAULT and self.persistent and fused_step is None and
+                               persistent is None) if deferred_value is None else bool(deferred_value)
         self.graph = None
         self.policy_events = None   # [(start, end)] HIP events around each policy launch (optional)
         self.env_events = None
@@ -128,9 +141,16 @@ class RolloutEngine:
             ev = self.policy_events
             if ev is not None:
                 ev[0][0].record()
-            self.policy.rollout_steps(env, tr.obs, self.rowproj, 0, True, tr.actions, tr.logp, tr.values,
-                                      tr.rewards, tr.dones, tr.info, seed=self.seed, offset=self._offset(0),
-                                      offset_stride=self.total, offset_dev=self.counter)
+            if self.deferred_value:  # the steps on the actor alone, then every window's value (V(s_T) too)
+                self.policy.rollout_actor_steps(env, tr.obs, self.rowproj, 0, True, tr.actions, tr.logp, tr.rewards,
+                                                tr.dones, tr.info, seed=self.seed, offset=self._offset(0),
+                                                offset_stride=self.total, offset_dev=self.counter)
+                self.policy.value_steps(tr.obs, self.rowproj, 0, tr.values,
+                                        tr.last_values if self.bootstrap else None)
+            else:
+                self.policy.rollout_steps(env, tr.obs, self.rowproj, 0, True, tr.actions, tr.logp, tr.values,
+                                          tr.rewards, tr.dones, tr.info, seed=self.seed, offset=self._offset(0),
+                                          offset_stride=self.total, offset_dev=self.counter)
             if ev is not None:
                 ev[0][1].record()
         for t in range(0 if self.persistent else self.T):
@@ -154,7 +174,13 @@ class RolloutEngine:
             if eev is not None:
                 eev[t][1].record()
         last = None
-        if self.bootstrap:
+        if self.bootstrap and self.deferred_value:  # value_steps wrote V(s_T); the event pair spans nothing
+            ev = self.policy_events
+            if ev is not None:
+                ev[self.T][0].record()
+                ev[self.T][1].record()
+            last = tr.last_values
+        elif self.bootstrap:
             if self.rowproj is not None and not _BOOTSTRAP_FULL:
                 # the critic alone (uavhip_policy_value_rows): nothing reads an action at step T; the
                 # actor ring row it skips is rebuilt by the next iteration's fill (step 0, fill=True)
