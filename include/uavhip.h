@@ -424,6 +424,33 @@ int uavhip_decode_steps(const uavhip_policy* policy, const uavhip_env* env, floa
 int uavhip_select_best(const uavhip_env* env, int32_t K, int32_t* best, double* J, int32_t* covered,
                        int32_t* assignment, uavhip_stream_t stream);
 
+/* Best-response local search on J(X) itself (k_refine, refine.hip): polish an allocation, build a
+ * non-learned baseline (start from the empty assignment), or only score an assignment from
+ * elsewhere (max_sweeps = 0). Row s < S uses the scene of env e = s * env_stride (its ACTIVE buffer;
+ * env_stride = K right after uavhip_select_best with K replicas). With list-order targets
+ * t = 0..M-1, P[u][t] = p_dmg[u][t] * p_pen[u] (the env step's pf), v = tgt_value, c = uav_cost,
+ * w = prm[UAVHIP_PRM_OMEGA] and an assignment a[u] in {-1, 0..M-1}:
+ *   J(a) = sum_t v[t] (1 - prod_{u: a[u] = t} (1 - P[u][t])) - w sum_{u: a[u] >= 0} c[u]
+ * (_calc_J_X, uav_env.py:244-269). One sweep visits u = 0..N-1 in order, every move visible to the
+ * next UAV: Q[t] = the product of (1.0 - P[w][t]) over the w != u with a[w] = t, ascending w, from
+ * 1.0; g[t] = (v[t] * Q[t]) * P[u][t] - (w * c[u]) in that order of operations, not contracted;
+ * g[-1] = 0.0; the candidate is the lowest index attaining the maximum over -1, 0, .., M-1; u moves
+ * to it iff its gain is strictly greater than g[a[u]]. g[t] is u's marginal contribution to J, so J
+ * never decreases in exact arithmetic. The search stops after a sweep without a move or after
+ * max_sweeps sweeps.
+ *  - assignment_in [S][N] int32 (nullable: every UAV starts at -1): target IDS (tgt_id, as
+ *    uavhip_select_best writes them) or -1; an id that matches no tgt_id of the scene counts as -1
+ *    and is counted in stats; of a duplicated id the lowest list index is taken;
+ *  - assignment_out [S][N] int32 (required; may alias assignment_in): target ids or -1;
+ *  - J [S] f64, covered [S] int32 = targets with at least one UAV (both required);
+ *  - stats [S][4] int32 (nullable): sweeps run, moves made, 1 if the last sweep made no move (or
+ *    max_sweeps = 0) else 0, invalid input ids.
+ * Needs env_stride >= 1, S >= 1, (S - 1) * env_stride < E, max_sweeps >= 0. The full N <= 64,
+ * M <= 128 range. The env's state and scene are only read. */
+int uavhip_refine_assignments(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t max_sweeps,
+                              const int32_t* assignment_in, int32_t* assignment_out, double* J,
+                              int32_t* covered, int32_t* stats, uavhip_stream_t stream);
+
 /* ---------------------------------------------------------------- PPO update (K5) */
 
 /* One clipped-PPO minibatch step of agents/ppo.py:96-169 (evaluate -> surrogate / clipped value

@@ -114,6 +114,8 @@ _SIGS = {
                                            _i32, _i32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp,
                                            _vp, _vp, _vp, _vp]),
     "uavhip_select_best": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _vp, _vp, _vp, _vp, _vp]),
+    "uavhip_refine_assignments": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp]),
     "uavhip_ppo_workspace_floats": (ctypes.c_int64, [_i32]),
     "uavhip_ppo_step": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "uavhip_episode_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),

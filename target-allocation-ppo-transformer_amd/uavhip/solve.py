@@ -12,8 +12,19 @@ learned constructive solver is used).
     alloc = solver.solve(num_scenes=4096, seed=0)       # or solve(scenes=[scene dicts])
     alloc.assignment[s]   # [N] target id of each UAV (-1: none), alloc.J[s], alloc.covered[s]
 
+    alloc = solver.solve(num_scenes=4096, seed=0, refine=32)   # + best-response local search on J
+    base = solver.baseline(num_scenes=4096, seed=0)            # the same scenes without the policy
+
+The env accepts or rejects an assignment on r(X), in one pass of the pointer walk; refine = R > 0
+polishes the chosen replica's allocation on J(X) itself (uavhip_refine_assignments: every UAV in turn
+moves to the target, or to none, where its marginal contribution to J is largest, at most R sweeps),
+and baseline() runs that search from the empty assignment -- the non-learned yardstick a
+checkpoint's mean J is read against.
+
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-prints one JSON line (mean / best J, mean covered, mean steps, scenes/s).
+[--refine SWEEPS] [--baseline] prints one JSON line (mean / best J, mean covered, mean steps,
+scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
+scenes where the policy beats the baseline).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
@@ -40,11 +51,13 @@ class Allocation:
     steps: torch.Tensor         # [S] int32: decode steps of the chosen replica
     replica_J: torch.Tensor     # [S, K] f64: J of every replica as decoding left it
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
+    decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
+    refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids
 
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
                             (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
-                             self.actions)))
+                             self.actions, self.decoded_J, self.refine_stats)))
 
 
 class AllocationSolver:
@@ -114,27 +127,45 @@ class AllocationSolver:
                 t.copy_(t[:S].repeat_interleave(K, dim=0))
         env.istate.zero_()
 
-    @torch.no_grad()
-    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False):
-        """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
-        `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
-        greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
-        the longest possible episode). Returns an Allocation."""
+    @staticmethod
+    def _scene_args(what, scenes, num_scenes, seed):
+        """The scene arguments of solve / baseline checked: (scenes list or None, S, seed)."""
         if (scenes is None) == (num_scenes is None):
-            raise ValueError("solve: pass scenes or num_scenes")
+            raise ValueError(f"{what}: pass scenes or num_scenes")
         if isinstance(scenes, dict):
             scenes = [scenes]
         S = len(scenes) if scenes is not None else int(num_scenes)
         if S <= 0:
-            raise ValueError("solve: no scenes")
-        seed = 0 if seed is None else int(seed)
+            raise ValueError(f"{what}: no scenes")
+        return scenes, S, 0 if seed is None else int(seed)
+
+    def _scene_env(self, scenes, S, seed):
+        """The env of S * K replicas with the scenes in place (the solver's device current)."""
+        env = self._size(S)
+        if scenes is not None:
+            self._load_host_scenes(env, scenes)
+        else:
+            self._generate_scenes(env, S, seed)
+        return env
+
+    @torch.no_grad()
+    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0):
+        """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
+        `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
+        greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
+        the longest possible episode). Returns an Allocation.
+        refine = R > 0: the chosen replica's assignment is polished by at most R sweeps of the
+        best-response local search on J (uavhip_refine_assignments); assignment / J / covered are
+        then the refined ones, decoded_J the J before and refine_stats the search's counters. A
+        scene where no replica finished (best_replica == -1) is refined from the empty assignment.
+        refine = 0 launches nothing more and changes nothing."""
+        refine = int(refine)
+        if refine < 0:
+            raise ValueError("solve: refine must be >= 0")
+        scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
         with torch.cuda.device(self.device):
-            env = self._size(S)
-            if scenes is not None:
-                self._load_host_scenes(env, scenes)
-            else:
-                self._generate_scenes(env, S, seed)
+            env = self._scene_env(scenes, S, seed)
             n_max = int(self.N * self.M if max_steps is None else max_steps)
             actions = torch.empty(n_max, env.E, dtype=torch.int8, device=env.device) if trace else None
             self.steps.zero_()
@@ -147,7 +178,25 @@ class AllocationSolver:
             best, J, covered, assignment = env.select_best(K)
             replica_J = env.dstate[:, _lib.DST["J"]].reshape(S, K).clone()
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
-        return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+            if refine == 0:
+                return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+            refined, rJ, rcov, stats = env.refine_assignments(assignment, stride=K, rows=S, max_sweeps=refine)
+        return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats)
+
+    @torch.no_grad()
+    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32):
+        """The non-learned yardstick for the same objective: the scenes solve() would run (scene for
+        scene under the same `seed`), no policy launch, the best-response local search started from
+        the empty assignment (a greedy constructor plus local search). Returns an Allocation whose
+        decode-only fields (best_replica, steps, replica_J) are zeros."""
+        scenes, S, seed = self._scene_args("baseline", scenes, num_scenes, seed)
+        K = self.K
+        with torch.cuda.device(self.device):
+            env = self._scene_env(scenes, S, seed)
+            assignment, J, covered, stats = env.refine_assignments(None, stride=K, rows=S, max_sweeps=max_sweeps)
+            zi = torch.zeros(S, dtype=torch.int32, device=env.device)
+            zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
+        return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
 
 
 def main(argv=None):
@@ -164,6 +213,11 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--uavs", type=int, default=default_cfg.NUM_UAVS)
     ap.add_argument("--targets", type=int, default=default_cfg.NUM_TARGETS)
+    ap.add_argument("--refine", type=int, default=0, metavar="SWEEPS",
+                    help="polish each allocation by at most SWEEPS sweeps of the best-response local search on J")
+    ap.add_argument("--baseline", action="store_true",
+                    help="also run the non-learned baseline (the local search from the empty assignment) on the "
+                         "same scenes and report the share of scenes where the policy's J is larger")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("uavhip.solve decodes on the GPU (HIP) only")
@@ -171,17 +225,23 @@ def main(argv=None):
     policy = TransformerActorCritic().to(dev)
     load_checkpoint(policy, a.checkpoint)
     solver = AllocationSolver(policy, a.uavs, a.targets, samples=a.samples)
-    solver.solve(num_scenes=a.scenes, seed=a.seed)  # warm-up: allocation, weight pack
+    solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine)  # warm-up: allocation, weight pack
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = solver.solve(num_scenes=a.scenes, seed=a.seed)
+    r = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     r = r.cpu()
-    print(json.dumps({"scenes": a.scenes, "samples": a.samples, "N": a.uavs, "M": a.targets, "seed": a.seed,
-                      "mean_J": float(r.J.mean()), "best_J": float(r.J.max()),
-                      "mean_covered": float(r.covered.double().mean()), "mean_steps": float(r.steps.double().mean()),
-                      "unfinished": int((r.best_replica < 0).sum()), "scenes_per_s": a.scenes / dt}))
+    out = {"scenes": a.scenes, "samples": a.samples, "N": a.uavs, "M": a.targets, "seed": a.seed,
+           "mean_J": float(r.J.mean()), "best_J": float(r.J.max()),
+           "mean_covered": float(r.covered.double().mean()), "mean_steps": float(r.steps.double().mean()),
+           "unfinished": int((r.best_replica < 0).sum()), "scenes_per_s": a.scenes / dt}
+    if a.refine > 0:
+        out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
+    if a.baseline:
+        b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
+        out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

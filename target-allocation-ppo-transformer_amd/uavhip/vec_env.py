@@ -247,6 +247,37 @@ class VecUAVEnv:
               "uavhip_select_best")
         return best, J, covered, assignment
 
+    def refine_assignments(self, assignment=None, stride=1, rows=None, max_sweeps=32, out=None, J=None, covered=None,
+                           stats=None):
+        """uavhip_refine_assignments: best-response local search on J(X) for `rows` scenes, row s on
+        the scene of env s * stride (rows defaults to every stride-th env; stride = K after
+        select_best(K)). assignment [rows, N] int32 target ids or -1 (None: start from the empty
+        assignment -- a greedy constructor plus local search); max_sweeps = 0 only scores it.
+        Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32,
+        stats [rows, 4] int32: sweeps, moves, converged, invalid input ids). out may be `assignment`
+        itself (in place). The env is only read."""
+        stride, max_sweeps = int(stride), int(max_sweeps)
+        if stride < 1:
+            raise ValueError(f"refine_assignments: stride={stride} must be >= 1")
+        S = (self.E - 1) // stride + 1 if rows is None else int(rows)
+        if S < 1 or (S - 1) * stride >= self.E:
+            raise ValueError(f"refine_assignments: rows={S} at stride={stride} do not fit E={self.E}")
+        if max_sweeps < 0:
+            raise ValueError(f"refine_assignments: max_sweeps={max_sweeps} must be >= 0")
+        dev = self.device
+        out = torch.empty(S, self.N, dtype=torch.int32, device=dev) if out is None else out
+        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
+        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
+        stats = torch.empty(S, 4, dtype=torch.int32, device=dev) if stats is None else stats
+        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
+        check_out(out, "out", torch.int32, (S, self.N), dev)
+        check_out(J, "J", torch.float64, (S,), dev)
+        check_out(covered, "covered", torch.int32, (S,), dev)
+        check_out(stats, "stats", torch.int32, (S, 4), dev)
+        check(LIB.uavhip_refine_assignments(self.desc, stride, S, max_sweeps, ptr(assignment), ptr(out), ptr(J),
+                                            ptr(covered), ptr(stats), stream_handle()), "uavhip_refine_assignments")
+        return out, J, covered, stats
+
     def episodes(self):
         return self.istate[:, _lib.IST["EPISODE"]]
 
