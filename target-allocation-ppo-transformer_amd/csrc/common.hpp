@@ -56,7 +56,7 @@ __device__ __forceinline__ int ffs64(unsigned long long m) { return __ffsll((lon
 // |x| >= 65520 (scripts/micro/f16_ovfl.hip: MODE.FP16_OVFL is 0 at kernel start), so x1 = inf and
 // x2 = -inf, every product that reads them is +-inf or NaN, and the next LayerNorm turns the token
 // row into NaN. What could hide that is a ReLU written as fmaxf (IEEE maxNum returns 0 for NaN):
-// the GEMM epilogues use relu_nan (policy.hip) instead, so overflow reaches the outputs.
+// the GEMM epilogues use relu_nan (policy_core.hpp) instead, so overflow reaches the outputs.
 __device__ __forceinline__ _Float16 f16_lo(float x, _Float16 x1) { return (_Float16)((x - (float)x1) * 2048.f); }
 // f16_lo's split four at a time as packed conversions: x1 = f16(x) once (v_cvt_pk_f16_f32), its fp32
 // value from the packed halves -- element by element, the compiler converted every x twice (once for

@@ -47,7 +47,7 @@ enum { INW = 0, INB, OUTW, OUTB, L1W, L1B, L2W, L2B, N1W, N1B, N2W, N2B };
 __host__ __device__ constexpr int layer_param(int trunk, int l, int which) { return trunk + 3 + kLayerParams * l + which; }
 
 // ---- split copies: the GEMM weights that run on the f16 matrix cores as fp32-accurate split
-// products (policy.hip, hgemm_tile) -- every encoder-layer GEMM, listed in the order the
+// products (policy_core.hpp, hgemm_tile) -- every encoder-layer GEMM, listed in the order the
 // kernels adopted them (the order fixes the packed offsets): the critic's layer-0
 // out-projection and FFN, and its layer-1 in_proj (K / V of every token, Q of position 4); the
 // layer-0 in_proj of both trunks for the rollout's window-row ring (the new row's Q | K | V); and the
@@ -130,7 +130,7 @@ __host__ __device__ constexpr int range_op(int trunk, int layer, int kind) {
 constexpr int kNumRangeOps = 10;
 static_assert(kRgOp + 2 * kNumRangeOps <= kRgSpare && kRgSpare <= kRangeFloats && kNumParams <= kRgE, "range table");
 __host__ __device__ constexpr int trunk_index(int trunk) { return trunk == kActorTrunk ? 0 : 1; }
-// The scales a kernel derives at start (policy.hip load_rtab -> Smem::rtab; the training forward
+// The scales a kernel derives at start (policy_core.hpp load_rtab -> Smem::rtab; the training forward
 // exports them, TrainIO::rtab_out, for the weight-gradient GEMM): the static operands' (2^-s, 2^s)
 // pairs, then layer 0's (14 max|W_e|, max|b_e| + max|pos|) and (D max|W_in|, max|b_in|) per trunk
 constexpr int kRtOp = 0, kRtE = 2 * kNumRangeOps, kRtA0 = kRtE + 4, kRtN = kRtA0 + 4;

@@ -26,10 +26,6 @@
 
 #include "policy_layout.hpp"  // the operand range bounds (range_exp / range_bound / range_entry)
 
-#ifndef UAVHIP_EXP
-#define UAVHIP_EXP 0  // timing experiments (A/B builds, results wrong): 51 no loads after the first two
-#endif                // slabs, 52 one MFMA of six, 53 no split arithmetic
-
 namespace uavhip {
 namespace tr {
 
@@ -191,10 +187,6 @@ __device__ __forceinline__ void wg_split_store(const f32x4 v, char* plane, int o
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         x1[j] = (_Float16)v[j];
-        if constexpr (UAVHIP_EXP == 53) {
-            x2[j] = x3[j] = x1[j];
-            continue;
-        }
         const float r1 = v[j] - (float)x1[j];                 // exact
         x2[j] = f16_lo(v[j], x1[j]);                          // = f16(r1 2^11)
         if constexpr (P3) x3[j] = (_Float16)((r1 - (float)x2[j] * (1.0f / 2048.0f)) * 4194304.f);  // exact
@@ -320,11 +312,6 @@ __device__ __forceinline__ void wg_kloop(char* wg_smem, const WgProb& P, int s0,
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     hi[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[a], b1[b], hi[a][b], 0, 0, 0);
-                    if constexpr (UAVHIP_EXP == 52 && P3) {  // keep the operands live
-                        mid[a][b] += __builtin_bit_cast(f32x4, a2[a]) + __builtin_bit_cast(f32x4, b2[b]);
-                        lo[a][b] += __builtin_bit_cast(f32x4, a3[a]) + __builtin_bit_cast(f32x4, b3[b]);
-                        continue;
-                    }
                     mid[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1[a], b2[b], mid[a][b], 0, 0, 0);
                     mid[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[a], b1[b], mid[a][b], 0, 0, 0);
                     if constexpr (P3) {
@@ -335,7 +322,7 @@ __device__ __forceinline__ void wg_kloop(char* wg_smem, const WgProb& P, int s0,
                 }
             if (s + 1 < n_slabs) {  // slab s + 1 (landed in registers meanwhile) -> the other stage
                 wg_stage_store<P3>(nx, wg_smem + ((s + 1) & 1) * kWgStageB, xmode, xg, xsc);
-                if (s + 2 < n_slabs && UAVHIP_EXP != 51) wg_gload(nx, P, (s0 + s + 2) * kWgBK, m0, n0);
+                if (s + 2 < n_slabs) wg_gload(nx, P, (s0 + s + 2) * kWgBK, m0, n0);
             }
             __syncthreads();  // the next stage is written; everyone is done reading this one
         }

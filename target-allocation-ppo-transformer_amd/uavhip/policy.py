@@ -387,7 +387,7 @@ def split_layout():
 def to_split_fragment_order(w):
     """[R][K] fp32 -> the split copy as float32 words: two fp16 planes w1 = f16(w),
     w2 = f16((w - w1) * 2^11) in blocks of 16 rows x 32 k (1 KiB of w1, then 1 KiB of w2), lane
-    l = r%16 + 16 ((k%32)//8) holding k%8 = 0..7 (the f16 MFMA operand layout, policy.hip hgemm_tile)."""
+    l = r%16 + 16 ((k%32)//8) holding k%8 = 0..7 (the f16 MFMA operand layout, policy_core.hpp hgemm_tile)."""
     R, K = w.shape
     w = w.to(torch.float32)
     w1 = w.to(torch.float16)  # IEEE round-to-nearest, inf beyond 65504: what the device conversions do

@@ -94,7 +94,7 @@ READELF = os.environ.get("READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason="needs llvm-readelf")
 def test_rollout_steps_carries_one_env_path(tmp_path):
-    """k_rollout_steps is instantiated per env-step path (policy.hip kEnvGrp / kEnvWave): with both
+    """k_rollout_steps is instantiated per env-step path (policy_block.hpp kEnvGrp / kEnvWave): with both
     paths compiled in it was 71 KB of code and spilled 28 VGPRs; the grouped instantiation the bench
     runs is 58.5 KB (62 KB since round 5's range scaling). Guard on its code size, so both paths do not
     creep back into one kernel."""

@@ -21,8 +21,8 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a
 # of <= 16 steps (resets inside groups); the grouped env path; T + 1 exactly one group; one short group
 SHAPES = [(33, 4, 4, 7, 5), (64, 16, 32, 11, 3), (96, 64, 64, 4, 0), (40, 8, 16, 1, 2)]
 ENV_STATE = ("istate", "dstate", "window", "nh_final", "nh_pure", "t_cost", "n_lock", "assigned")
-ACTOR_ROW = 2 * 128  # a ring row: actor K | V, then critic Q | K | V (policy.hip kRowFloats)
-POS_TABLE = 2 * 5 * 384  # the Win pos_s table in front of the ring (policy.hip kPposFloats)
+ACTOR_ROW = 2 * 128  # a ring row: actor K | V, then critic Q | K | V (policy_encoder.hpp kRowFloats)
+POS_TABLE = 2 * 5 * 384  # the Win pos_s table in front of the ring (policy_encoder.hpp kPposFloats)
 
 
 @functools.lru_cache(maxsize=None)
