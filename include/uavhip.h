@@ -511,6 +511,34 @@ int uavhip_ppo_step(const uavhip_ppo* ppo, const float* states, const int8_t* ac
                     const float* old_values, const float* returns, const float* advantages, const int32_t* idx,
                     int32_t phases, uavhip_stream_t stream);
 
+/* Update diagnostics of a batch of n samples (csrc/ppo_diag.hip), out[UAVHIP_DIAG_COUNT] f64. With
+ * d_i = (double)new_logp_i - (double)old_logp_i and r_i = exp(d_i), all arithmetic in double: */
+enum uavhip_diag {
+    UAVHIP_DIAG_APPROX_KL = 0,   /* mean of (r_i - 1) - d_i                                         */
+    UAVHIP_DIAG_CLIP_FRAC,       /* share of samples with |r_i - 1| > eps_clip (ppo.py:137's clamp)  */
+    UAVHIP_DIAG_RATIO_MAX,       /* max of r_i (a NaN ratio is skipped: it shows in NONFINITE)       */
+    UAVHIP_DIAG_RATIO_MEAN,      /* mean of r_i                                                      */
+    UAVHIP_DIAG_VALUE_CLIP_FRAC, /* share with |new_value_i - old_value_i| > eps_clip (ppo.py:143)   */
+    UAVHIP_DIAG_EXPLAINED_VAR,   /* 1 - Var(R - V_old) / Var(R); NaN when Var(R) == 0                */
+    UAVHIP_DIAG_NONFINITE,       /* number of samples whose d_i is not finite                        */
+    UAVHIP_DIAG_RETURN_VAR,      /* Var(R), population variance (exactly 0 for constant returns)     */
+    UAVHIP_DIAG_RESIDUAL_VAR,    /* Var(R - V_old), population variance                              */
+    UAVHIP_DIAG_COUNT
+};
+
+/* Doubles of the partials buffer uavhip_ppo_diagnostics needs for n samples (-1 for n < 1). */
+int32_t uavhip_ppo_diagnostics_partials(int64_t n);
+
+/* old_logp / new_logp / old_value / new_value / returns [n] f32. Two launches: per-block partials in
+ * a fixed order (no atomics), then one block that merges them in index order, so the results are
+ * bitwise repeatable and the call can be captured. The variances carry (count, mean, M2) per
+ * partial, merged with the pairwise update formula. Non-finite inputs propagate into the sums and
+ * are counted; nothing is clamped. partials: caller-owned, partials_doubles >=
+ * uavhip_ppo_diagnostics_partials(n). */
+int uavhip_ppo_diagnostics(const float* old_logp, const float* new_logp, const float* old_value,
+                           const float* new_value, const float* returns, int64_t n, double eps_clip,
+                           double* partials, int32_t partials_doubles, double* out, uavhip_stream_t stream);
+
 /* ---------------------------------------------------------------- episode metrics */
 
 /* Per-episode sums main_train.py logs (:122-136, :161-195), one record per finished episode. */

@@ -41,6 +41,9 @@ PPO_FORWARD, PPO_BACKWARD, PPO_UPDATE, PPO_FULL, PPO_PACKED = 1, 2, 4, 7, 8
 EP = dict(ENV=0, EPISODE=1, STEPS=2, REWARD=3, Q0=4, J_SUM=5, MAX_COV=6, ACTION1=7, VALID=8, PDMG_SUM=9,
           PFINAL_SUM=10, ASSIGN_STEPS=11)
 EP_COUNT = 12
+DIAG = dict(APPROX_KL=0, CLIP_FRAC=1, RATIO_MAX=2, RATIO_MEAN=3, VALUE_CLIP_FRAC=4, EXPLAINED_VAR=5, NONFINITE=6,
+            RETURN_VAR=7, RESIDUAL_VAR=8)
+DIAG_COUNT = 9
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -118,6 +121,9 @@ _SIGS = {
                                                  _vp]),
     "uavhip_ppo_workspace_floats": (ctypes.c_int64, [_i32]),
     "uavhip_ppo_step": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "uavhip_ppo_diagnostics_partials": (_i32, [ctypes.c_int64]),
+    "uavhip_ppo_diagnostics": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, _vp, _i32, _vp,
+                                              _vp]),
     "uavhip_episode_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "uavhip_device_pci_id": (ctypes.c_int, [_i32, ctypes.c_char_p, _i32]),
     "uavhip_device_from_pci_id": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(_i32)]),

@@ -57,6 +57,74 @@ def gae_workspace(T, E, device):
             torch.empty(2 * npart, dtype=torch.float64, device=device), torch.empty(2, dtype=torch.float64, device=device))
 
 
+#: update_diagnostics runs the fused forward in launches of at most this many windows: the forward's
+#: window offsets are 32-bit (B * 70 floats), so a single launch covers every B up to here
+DIAG_FORWARD_CHUNK = 1 << 22
+
+
+def ppo_diagnostics(old_logp, new_logp, old_values, new_values, returns, eps_clip=None, out=None, partials=None):
+    """uavhip_ppo_diagnostics on [n] f32 device tensors -> out [DIAG_COUNT] f64 on the device (slots:
+    _lib.DIAG). All arithmetic in double, fixed reduction order (bitwise repeatable, capturable).
+    partials: a float64 workspace of uavhip_ppo_diagnostics_partials(n) elements (allocated if None)."""
+    from . import _lib
+    from .vec_env import check_out
+    dev = old_logp.device
+    if dev.type != "cuda":
+        raise RuntimeError("ppo_diagnostics runs on the GPU (HIP) only")
+    n = old_logp.numel()
+    if n < 1:
+        raise ValueError("ppo_diagnostics: need at least one sample")
+    for t, name in ((old_logp, "old_logp"), (new_logp, "new_logp"), (old_values, "old_values"),
+                    (new_values, "new_values"), (returns, "returns")):
+        check_out(t, name, torch.float32, (n,), dev)
+    need = int(LIB.uavhip_ppo_diagnostics_partials(n))
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float64, device=dev)
+    elif partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < need or \
+            partials.device != dev:
+        raise ValueError(f"partials: need a contiguous float64 buffer of at least {need} elements on {dev}")
+    out = torch.empty(_lib.DIAG_COUNT, dtype=torch.float64, device=dev) if out is None else out
+    check_out(out, "out", torch.float64, (_lib.DIAG_COUNT,), dev)
+    eps = cfg.EPS_CLIP if eps_clip is None else eps_clip
+    check(LIB.uavhip_ppo_diagnostics(ptr(old_logp), ptr(new_logp), ptr(old_values), ptr(new_values), ptr(returns), n,
+                                     ctypes.c_double(eps), ptr(partials), partials.numel(), ptr(out),
+                                     stream_handle()), "uavhip_ppo_diagnostics")
+    return out
+
+
+@torch.no_grad()
+def update_diagnostics(policy, states, actions, old_logp, old_values, returns, eps_clip=None, out=None,
+                       workspace=None):
+    """Diagnostics of the current `policy` against the batch an update was (or is being) run on:
+    approximate KL, clip fractions, ratio max / mean, explained variance, non-finite count
+    (include/uavhip.h uavhip_diag). Runs policy.fused_forward(states, actions=actions) over the whole
+    batch -- one launch up to DIAG_FORWARD_CHUNK windows, chunks of that size beyond -- then
+    uavhip_ppo_diagnostics. Returns a dict of 0-dim device tensors keyed by the lower-case slot names,
+    or the `out` tensor ([DIAG_COUNT] f64) when one is given. Nothing the rollout reads is written:
+    the policy's sampling counter is left where it was.
+    workspace: optional (new_logp [n] f32, new_values [n] f32, partials f64) buffers to reuse."""
+    from . import _lib
+    n = old_logp.numel()
+    dev = old_logp.device
+    states = states.reshape(n, cfg.SEQ_LEN, cfg.STATE_DIM)
+    actions = actions.reshape(n)
+    if workspace is None:
+        new_logp = torch.empty(n, dtype=torch.float32, device=dev)
+        new_values = torch.empty(n, dtype=torch.float32, device=dev)
+        partials = None
+    else:
+        new_logp, new_values, partials = workspace
+    for b0 in range(0, n, DIAG_FORWARD_CHUNK):
+        b1 = min(n, b0 + DIAG_FORWARD_CHUNK)
+        policy.fused_forward(states[b0:b1], actions=actions[b0:b1], logp=new_logp[b0:b1], value=new_values[b0:b1],
+                             offset=0)
+    res = ppo_diagnostics(old_logp.reshape(n), new_logp, old_values.reshape(n), new_values, returns.reshape(n),
+                          eps_clip=eps_clip, out=out, partials=partials)
+    if out is not None:
+        return out
+    return {k.lower(): res[i] for k, i in _lib.DIAG.items()}
+
+
 def ppo_epochs(policy, optimizer, states, actions, old_logprobs, old_values, returns, advantages, epochs=None,
                batch_size=None, eps_clip=None, grad_clip=None, generator=None, perms=None, on_step=None):
     """Clipped-PPO minibatch epochs (ppo.py:96-169). Returns (mean actor loss, critic loss, entropy, n).
