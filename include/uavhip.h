@@ -451,6 +451,36 @@ int uavhip_refine_assignments(const uavhip_env* env, int32_t env_stride, int32_t
                               const int32_t* assignment_in, int32_t* assignment_out, double* J,
                               int32_t* covered, int32_t* stats, uavhip_stream_t stream);
 
+/* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
+ * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
+ * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is
+ * a function of the env's pointer (u, t) alone:
+ *   a = (teach[u] == t) ? 1 : 0,   teach[u] = the list index of UAV u's target, or -1,
+ * and the step is the env step with UAVHIP_STEP_HOLD (bitwise the step uavhip_env_step takes for the
+ * same action). The env decides: an assign it rejects (r(X') < r(X)) walks on to t + 1, and that UAV
+ * stays unassigned for the rest of the episode (its teacher index is behind the pointer).
+ *  - assignment [E][N] int32 (required): target IDS (tgt_id of the env's ACTIVE scene buffer, as
+ *    uavhip_select_best / uavhip_refine_assignments write them) or -1, converted as
+ *    uavhip_refine_assignments converts them: an id that matches no tgt_id counts as -1 and is
+ *    counted in stats; of a duplicated id the lowest list index is taken;
+ *  - every env starts from its CURRENT state (the caller has reset it); an env already finished
+ *    (istate[UAV_IDX] >= N) is held from step 0; afterwards the env is stepped -- it holds the
+ *    allocation it accepted, as after a decode;
+ *  - outputs, time-major, each nullable: obs [n_max][E][5][14] f32 -- obs[t] is the window step t's
+ *    action was decided on: obs[0] the env's own window at entry, obs[t + 1] what step t emitted;
+ *    actions [n_max][E] int8 (0 / 1); reward [n_max][E] f64; done [n_max][E] u8;
+ *    info [n_max][E][UAVHIP_INFO_COUNT] f64. In the rows at or past an env's end (held rows): a zero
+ *    window, action -1, reward 0, done 1, info 0;
+ *  - steps [E] int32 (required): ADDED to; finished [E] u8 (required): written; ep_return [E] f64
+ *    (nullable): the rewards ADDED to it in step order -- all three as uavhip_decode_steps;
+ *  - stats [E][2] int32 (nullable), written: teacher assigns the env rejected in this call (action-1
+ *    steps that left the allocation unchanged, reward 0), invalid input ids.
+ * Needs n_max >= 1 (N * M bounds every episode). The full N <= 64, M <= 128 range; f32 observations
+ * only (UAVHIP_EINVAL under UAVHIP_ENV_OBS_F16). */
+int uavhip_teacher_steps(const uavhip_env* env, const int32_t* assignment, int32_t n_max, float* obs,
+                         int8_t* actions, double* reward, uint8_t* done, double* info, int32_t* steps,
+                         uint8_t* finished, double* ep_return, int32_t* stats, uavhip_stream_t stream);
+
 /* ---------------------------------------------------------------- PPO update (K5) */
 
 /* One clipped-PPO minibatch step of agents/ppo.py:96-169 (evaluate -> surrogate / clipped value

@@ -8,6 +8,7 @@
     PPOAgent           agents/ppo.py API
     AllocationSolver   batched inference: actor-only decode to the episode end, best of K (solve.py)
     TrainingRun        the training loop: rollout + update + diagnostics + evaluation, resumable (fit.py)
+    ImitationRun       imitation warm start: teacher-forced episodes of the baseline search (imitate.py)
     load_checkpoint    the reference's torch.save(state_dict) files, older architectures reported
 
 Importing this package loads libuavhip.so and raises if it is missing: there is no CPU fallback.
@@ -31,9 +32,12 @@ def __getattr__(name):
     if name == "TrainingRun":  # fit.py is a command line too (python -m uavhip.fit)
         from . import fit
         return fit.TrainingRun
+    if name in ("ImitationRun", "TeacherBatch"):  # and imitate.py (python -m uavhip.imitate)
+        from . import imitate
+        return getattr(imitate, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 __all__ = ["LIB", "UavHipError", "Config", "cfg", "TransformerActorCritic", "pack_weights", "PPOAgent", "gae",
            "RolloutEngine", "Trajectory", "VecUAVEnv", "load_checkpoint", "save_checkpoint", "Allocation",
-           "AllocationSolver", "TrainingRun"]
+           "AllocationSolver", "TrainingRun", "ImitationRun", "TeacherBatch"]

@@ -4,9 +4,10 @@ evaluation -> progress line -> checkpoints, iteration after iteration, on one GP
     run = TrainingRun(envs=4096, uavs=16, targets=32, horizon=64, minibatch=4096, out_dir="runs/a", seed=0)
     run.fit(iterations=200)                      # writes runs/a/final_model.pth, progress.jsonl, state_it200.pt
     TrainingRun(..., out_dir="runs/a", resume="runs/a").fit(iterations=200)   # continues, bit for bit
+    TrainingRun(..., out_dir="runs/b", init="runs/clone/final_model.pth")     # starts from a checkpoint (uavhip.imitate)
 
     python -m uavhip.fit --envs 4096 --uavs 16 --targets 32 --horizon 64 --minibatch 4096 \
-        --iterations 200 --out runs/a [--resume runs/a]      # prints one JSON line at the end
+        --iterations 200 --out runs/a [--resume runs/a | --init model.pth]   # prints one JSON line at the end
 
 One iteration: RolloutEngine.collect() (a hipGraph replay), EpisodeStats.update(traj),
 FusedPPOTrainer.run() over all T * E transitions (the trainer's buffers are views of the engine's
@@ -136,10 +137,17 @@ class TrainingRun:
     def __init__(self, envs, uavs, targets, horizon, minibatch, out_dir, seed=0, epochs=None, target_kl=None,
                  diagnostics_every=1, eval_every=0, eval_scenes=1024, eval_seed=1, checkpoint_every=0,
                  reset_episodes=None, resume=None, lr_actor=None, lr_critic=None, eps_clip=None, max_grad_norm=None,
-                 value_coef=0.5, entropy_coef=0.01, device="cuda:0"):
+                 value_coef=0.5, entropy_coef=0.01, device="cuda:0", init=None):
         """target_kl: run the update epoch by epoch and drop the remaining epochs once the
         diagnostics' APPROX_KL exceeds it (None: one run() call of `epochs` epochs).
-        resume: a state file, or a run directory (its latest state)."""
+        resume: a state file, or a run directory (its latest state).
+        init: a policy checkpoint (checkpoint.save_checkpoint's format, e.g. uavhip.imitate's
+        final_model.pth) loaded into the seeded policy before training starts; everything else is
+        seeded as without it. Not with resume (a state carries its own parameters), and not a
+        hyper-parameter: state files do not record it."""
+        if init is not None and resume is not None:
+            raise ValueError("init and resume exclude each other: a resumed state carries its own parameters")
+        self.init = None if init is None else str(init)
         self.E, self.N, self.M, self.T = int(envs), int(uavs), int(targets), int(horizon)
         self.minibatch = int(minibatch)
         validate_shape(self.E, self.N, self.M, self.T, self.minibatch, int(eval_every))
@@ -196,6 +204,9 @@ class TrainingRun:
         torch.cuda.set_device(dev)
         torch.manual_seed(self.seed)
         self.policy = TransformerActorCritic().to(dev)
+        if self.init is not None:  # before the trainer takes its flat views of the parameters
+            from .checkpoint import load_checkpoint
+            load_checkpoint(self.policy, self.init)
         self.env = VecUAVEnv(self.E, self.N, self.M, device=dev, seed=self.seed,
                              full_reset_period=h["reset_episodes"])
         self.engine = RolloutEngine(self.env, self.policy, self.T, seed=self.seed)
@@ -429,11 +440,13 @@ def main(argv=None):
     ap.add_argument("--reset-episodes", type=int, default=None,
                     help=f"episodes between fresh scenes (default {cfg.RESET_EPISODES})")
     ap.add_argument("--resume", default=None, help="a state_it{K}.pt file, or a run directory (its latest state)")
+    ap.add_argument("--init", default=None,
+                    help="a policy checkpoint to start from (uavhip.imitate's final_model.pth); not with --resume")
     a = ap.parse_args(argv)
     run = TrainingRun(a.envs, a.uavs, a.targets, a.horizon, a.minibatch, a.out, seed=a.seed, epochs=a.epochs,
                       target_kl=a.target_kl, diagnostics_every=a.diagnostics_every, eval_every=a.eval_every,
                       eval_scenes=a.eval_scenes, eval_seed=a.eval_seed, checkpoint_every=a.checkpoint_every,
-                      reset_episodes=a.reset_episodes, resume=a.resume)
+                      reset_episodes=a.reset_episodes, resume=a.resume, init=a.init)
     print(json.dumps(run.fit(a.iterations)))
 
 

@@ -1,0 +1,272 @@
+"""Imitation warm start: clone the non-learned baseline (the best-response search on J) into the
+policy, from teacher-forced episodes.
+
+    run = ImitationRun(envs=4096, uavs=16, targets=32, minibatch=4096, out_dir="runs/clone", seed=0)
+    run.fit(iterations=20)                       # writes runs/clone/final_model.pth and progress.jsonl
+    TrainingRun(..., init="runs/clone/final_model.pth").fit(...)        # PPO from the clone (uavhip.fit)
+
+    python -m uavhip.imitate --envs 4096 --uavs 16 --targets 32 --minibatch 4096 --iterations 20 --out runs/clone
+    python -m uavhip.fit ... --init runs/clone/final_model.pth
+
+One iteration: fresh on-device scenes, the teacher allocation of every scene
+(VecUAVEnv.refine_assignments from the empty assignment: AllocationSolver.baseline's search), ONE
+uavhip_teacher_steps launch that walks every env along its teacher allocation and records the window
+each action was decided on, the action and the env's reward (teacher_batch), then epochs of the
+existing fused PPO step over the valid rows (imitation_update).
+
+The update needs no kernel of its own. With advantage A = 1 and old_logp = the current policy's
+log-probability of the teacher's action, the ratio is 1 at the first step, min(r A, clip(r) A) = r,
+and its gradient is the gradient of log pi(a*|s): likelihood ascent on the teacher's actions. As the
+epochs move the policy, rows whose ratio has left [1 - eps, 1 + eps] upwards stop contributing: the
+clip is a trust region per batch. old_values = the current values, so the clipped value loss is the
+plain (v - R)^2 at the first step, R the discounted return-to-go of the teacher's episode.
+
+Seeding contract (tests/test_gpu_imitate.py relies on it): torch.manual_seed(seed) before
+TransformerActorCritic(); iteration i = 1, 2, .. draws its scenes with env.desc.seed = seed + i (as
+AllocationSolver._generate_scenes sets it) after zeroing istate; minibatch orders from
+torch.Generator().manual_seed(seed), continuing across iterations: torch.randperm(rows) per epoch.
+Same seed, same parameters, bit for bit. An ImitationRun cannot be resumed.
+"""
+import json
+import os
+import time
+from dataclasses import dataclass
+
+import torch
+
+from .config import cfg
+
+PROGRESS_FIELDS = ("iteration", "rows", "nll_before", "nll_after", "agreement", "teacher_mean_J", "rejected")
+EVAL_FIELDS = ("eval_mean_J", "eval_mean_J_baseline", "eval_beats_baseline")
+
+
+@dataclass
+class TeacherBatch:
+    obs: torch.Tensor        # [n_max, E, 5, 14] f32: obs[t] is the window step t's action was decided on
+    actions: torch.Tensor    # [n_max, E] int8: the teacher's action, -1 at or past an env's end
+    returns: torch.Tensor    # [n_max, E] f32: discounted return-to-go, 0 in held rows
+    rows: torch.Tensor       # [rows] int32: flat indices (t * E + e) of the valid rows, ascending
+    steps: torch.Tensor      # [E] int32: episode lengths
+    J: torch.Tensor          # [E] f64: J of the allocation the env accepted (dstate[J])
+    teacher_J: torch.Tensor  # [E] f64: J of the teacher allocation (uavhip_refine_assignments')
+    rejected: torch.Tensor   # [E] int32: teacher assigns the env rejected
+
+
+@torch.no_grad()
+def teacher_batch(env, assignment=None, max_sweeps=32, gamma=None):
+    """Reset `env`, walk it along `assignment` ([E, N] int32 target ids or -1; None: the baseline,
+    env.refine_assignments(None, max_sweeps=max_sweeps)) in one uavhip_teacher_steps launch of N * M
+    steps, and return the episodes as a TeacherBatch. returns = uavhip.ppo.gae with zero values and
+    lambda = 1: ret_t = r_t + gamma (1 - done_t) ret_{t+1}."""
+    from . import _lib
+    from .ppo import gae
+    env.reset()
+    if assignment is None:
+        assignment, teacher_J, _, _ = env.refine_assignments(None, max_sweeps=max_sweeps)
+    else:
+        _, teacher_J, _, _ = env.refine_assignments(assignment, max_sweeps=0)
+    out = env.teacher_steps(assignment)
+    returns, _, _ = gae(out["reward"], out["done"], torch.zeros_like(out["reward"], dtype=torch.float32),
+                        gamma=cfg.GAMMA if gamma is None else gamma, lam=1.0, normalize=False)
+    rows = torch.nonzero(out["actions"].reshape(-1) >= 0).reshape(-1).to(torch.int32)
+    return TeacherBatch(out["obs"], out["actions"], returns, rows, out["steps"],
+                        env.dstate[:, _lib.DST["J"]].clone(), teacher_J, out["stats"][:, 0].clone())
+
+
+def _forward(policy, states, actions):
+    """(logp, value, logits) of the teacher's actions on `states`, counter-neutral (offset = 0)."""
+    from .ppo import DIAG_FORWARD_CHUNK
+    n, dev = states.shape[0], states.device
+    logp = torch.empty(n, dtype=torch.float32, device=dev)
+    value = torch.empty(n, dtype=torch.float32, device=dev)
+    logits = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    for b0 in range(0, n, DIAG_FORWARD_CHUNK):
+        b1 = min(n, b0 + DIAG_FORWARD_CHUNK)
+        policy.fused_forward(states[b0:b1], actions=actions[b0:b1], logp=logp[b0:b1], value=value[b0:b1],
+                             logits=logits[b0:b1], offset=0)
+    return logp, value, logits
+
+
+def _fit_quality(logp, logits, actions):
+    """(mean negative log-likelihood of the teacher's actions, share of rows whose greedy action
+    (l1 > l0, a tie gives 0: the decode's rule) is the teacher's, the same share over the teacher's
+    action-1 rows alone -- NaN without one), as 0-dim f64 device tensors."""
+    greedy = (logits[:, 1] > logits[:, 0]).to(torch.int8)
+    hit = (greedy == actions).double()
+    return -logp.double().mean(), hit.mean(), hit[actions == 1].mean()
+
+
+@torch.no_grad()
+def build_batch(policy, batch, assign_weight=1.0, pad_to=1):
+    """The update's buffers over the valid rows of `batch`, in row order: (states [n, 5, 14],
+    actions [n] int8, old_logp [n], old_values [n], returns [n], advantages [n]) f32, rows, and the
+    forward's logits [rows, 2]. old_logp / old_values come from one policy.fused_forward(states,
+    actions=teacher); advantages are 1.0, assign_weight on the action-1 rows, not normalised. n is
+    rows rounded up to a multiple of pad_to; the rows past `rows` are zeros and no minibatch may
+    index them."""
+    k = int(batch.rows.numel())
+    if k < 1:
+        raise ValueError("imitation: the teacher batch has no valid row")
+    idx = batch.rows.long()
+    states = batch.obs.reshape(-1, cfg.SEQ_LEN, cfg.STATE_DIM)[idx]
+    actions = batch.actions.reshape(-1)[idx]
+    returns = batch.returns.reshape(-1)[idx]
+    logp, value, logits = _forward(policy, states, actions)
+    adv = torch.where(actions == 1, float(assign_weight), 1.0).to(torch.float32)
+    n = -(-k // int(pad_to)) * int(pad_to)
+    bufs = (states, actions, logp, value, returns, adv)
+    if n > k:
+        bufs = tuple(torch.cat([t, t.new_zeros((n - k,) + tuple(t.shape[1:]))]) for t in bufs)
+    return bufs, k, logits
+
+
+def imitation_update(trainer, policy, batch, epochs, generator, assign_weight=1.0, use_graph=False):
+    """`epochs` epochs of the fused PPO step (trainer: a FusedPPOTrainer on `policy`) over the valid
+    rows of `batch` as a likelihood fit of the teacher's actions (module docstring). Each epoch draws
+    torch.randperm(rows, generator); the last minibatch of an epoch is filled with idx -1 padding
+    rows, which add nothing. Returns {"rows", "nll_before", "nll_after", "agreement_before",
+    "agreement", "assign_agreement", "optimizer_steps"}: the mean negative log-likelihood of the
+    teacher's actions and the share of rows whose greedy action is the teacher's, before and after,
+    and that share after over the action-1 rows alone (most rows are skips: a policy that never
+    assigns already agrees on their share). Forwards with offset = 0: the policy's sampling counter
+    does not move."""
+    mb = trainer.global_minibatch
+    bufs, k, logits = build_batch(policy, batch, assign_weight, pad_to=mb)
+    nll0, agree0, _ = _fit_quality(bufs[2][:k], logits, bufs[1][:k])
+    trainer.set_buffers(*bufs)
+    n = bufs[0].shape[0]
+    pad = torch.full((n - k,), -1, dtype=torch.int32)
+    perms = [torch.cat([torch.randperm(k, generator=generator).to(torch.int32), pad]) for _ in range(int(epochs))]
+    _, _, _, cnt = trainer.run(perms=perms, use_graph=use_graph)
+    logp, _, logits = _forward(policy, bufs[0][:k], bufs[1][:k])
+    nll1, agree1, assign1 = _fit_quality(logp, logits, bufs[1][:k])
+    q = torch.stack([nll0, nll1, agree0, agree1, assign1]).tolist()
+    return {"rows": k, "nll_before": q[0], "nll_after": q[1], "agreement_before": q[2], "agreement": q[3],
+            "assign_agreement": q[4], "optimizer_steps": int(cnt)}
+
+
+def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0):
+    """ImitationRun's argument checks that need no device; each message names the argument."""
+    if minibatch <= 0 or minibatch % 64:
+        raise ValueError(f"minibatch={minibatch}: must be a positive multiple of 64 (the training step's tile)")
+    if envs <= 0:
+        raise ValueError(f"envs={envs} must be positive")
+    if not (1 <= uavs <= 64 and 1 <= targets <= 128):
+        raise ValueError(f"uavs={uavs} (1..64) / targets={targets} (1..128) out of range")
+    if epochs < 1:
+        raise ValueError(f"epochs={epochs}: must be >= 1")
+    if eval_every < 0:
+        raise ValueError(f"eval_every={eval_every}: must be >= 0 (0 = off)")
+    if eval_every > 0 and (uavs > 64 or targets > 64):
+        raise ValueError(f"eval_every={eval_every}: the evaluation decodes with N, M <= 64 "
+                         f"(uavs={uavs}, targets={targets}); pass eval_every=0")
+
+
+class ImitationRun:
+    def __init__(self, envs, uavs, targets, minibatch, out_dir, seed=0, epochs=None, eval_every=0, eval_scenes=1024,
+                 eval_seed=1, max_sweeps=32, assign_weight=1.0, lr_actor=None, lr_critic=None, eps_clip=None,
+                 max_grad_norm=None, value_coef=0.5, entropy_coef=0.01, device="cuda:0"):
+        self.E, self.N, self.M = int(envs), int(uavs), int(targets)
+        self.minibatch = int(minibatch)
+        self.epochs = int(cfg.K_EPOCHS if epochs is None else epochs)
+        self.eval_every = int(eval_every)
+        validate_args(self.E, self.N, self.M, self.minibatch, self.epochs, self.eval_every)
+        self.eval_scenes, self.eval_seed = int(eval_scenes), int(eval_seed)
+        self.max_sweeps, self.assign_weight = int(max_sweeps), float(assign_weight)
+        self.seed = int(seed)
+        self.out_dir = str(out_dir)
+        if not torch.cuda.is_available():
+            raise RuntimeError("uavhip.imitate trains on the GPU (HIP) only")
+        from .policy import TransformerActorCritic
+        from .train import FusedPPOTrainer
+        from .vec_env import VecUAVEnv
+        self.device = dev = torch.device(device)
+        os.makedirs(self.out_dir, exist_ok=True)
+        torch.cuda.set_device(dev)
+        torch.manual_seed(self.seed)
+        self.policy = TransformerActorCritic().to(dev)
+        self.env = VecUAVEnv(self.E, self.N, self.M, device=dev, seed=self.seed, full_reset_period=0, scene_buffers=1)
+        self.trainer = FusedPPOTrainer(self.policy, self.minibatch, lr_actor=lr_actor, lr_critic=lr_critic,
+                                       eps_clip=eps_clip, max_grad_norm=max_grad_norm, value_coef=value_coef,
+                                       entropy_coef=entropy_coef)
+        self.generator = torch.Generator().manual_seed(self.seed)
+        self.iteration = 0
+        self.wall_s = 0.0
+        self.last = None
+        self.solver = None
+        self.baseline_J = None
+
+    def _evaluate(self):
+        from .solve import AllocationSolver
+        if self.solver is None:
+            self.solver = AllocationSolver(self.policy, self.N, self.M, samples=1)
+            self.baseline_J = self.solver.baseline(num_scenes=self.eval_scenes, seed=self.eval_seed).J.clone()
+        J = self.solver.solve(num_scenes=self.eval_scenes, seed=self.eval_seed).J
+        return {"eval_mean_J": float(J.mean()), "eval_mean_J_baseline": float(self.baseline_J.mean()),
+                "eval_beats_baseline": float((J > self.baseline_J).double().mean())}
+
+    def step(self):
+        """One iteration; returns the progress line's fields (also appended to progress.jsonl)."""
+        from .fit import progress_line
+        t0 = time.perf_counter()
+        self.iteration += 1
+        it, env = self.iteration, self.env
+        env.desc.seed = (self.seed + it) & (2 ** 64 - 1)
+        env.istate.zero_()
+        env.generate_scenes()
+        batch = teacher_batch(env, None, max_sweeps=self.max_sweeps)
+        q = imitation_update(self.trainer, self.policy, batch, self.epochs, self.generator, self.assign_weight)
+        f = {"iteration": it, "rows": q["rows"], "nll_before": q["nll_before"], "nll_after": q["nll_after"],
+             "agreement": q["agreement"], "teacher_mean_J": float(batch.teacher_J.mean()),
+             "rejected": int(batch.rejected.sum()), "agreement_before": q["agreement_before"],
+             "assign_agreement": q["assign_agreement"], "assign_share": float((batch.actions == 1).sum()) / q["rows"],
+             "walked_mean_J": float(batch.J.mean()), "optimizer_steps": q["optimizer_steps"]}
+        if self.eval_every > 0 and it % self.eval_every == 0:
+            f.update(self._evaluate())
+        self.wall_s += time.perf_counter() - t0
+        f["wall_s"] = self.wall_s
+        with open(os.path.join(self.out_dir, "progress.jsonl"), "a") as fh:
+            fh.write(progress_line(f) + "\n")
+        self.last = f
+        return f
+
+    def fit(self, iterations):
+        """Run `iterations` iterations in total, then write final_model.pth (the reference's
+        checkpoint format: uavhip.solve and uavhip.fit --init load it). Returns the summary the
+        command line prints."""
+        from .checkpoint import save_checkpoint
+        from .fit import _json_value
+        while self.iteration < int(iterations):
+            self.step()
+        torch.cuda.synchronize(self.device)
+        final = os.path.join(self.out_dir, "final_model.pth")
+        save_checkpoint(self.policy, final)
+        return {"out": self.out_dir, "iterations": self.iteration, "final_model": final, "wall_s": self.wall_s,
+                "last": None if self.last is None else {k: _json_value(v) for k, v in self.last.items()}}
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="Clone the best-response baseline into the policy (imitation warm start)")
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--uavs", type=int, default=cfg.NUM_UAVS)
+    ap.add_argument("--targets", type=int, default=cfg.NUM_TARGETS)
+    ap.add_argument("--minibatch", type=int, default=4096)
+    ap.add_argument("--iterations", type=int, required=True)
+    ap.add_argument("--out", required=True, help="run directory")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--epochs", type=int, default=None, help=f"update epochs per iteration (default {cfg.K_EPOCHS})")
+    ap.add_argument("--assign-weight", type=float, default=1.0, help="advantage of the action-1 (assign) rows")
+    ap.add_argument("--max-sweeps", type=int, default=32, help="sweeps of the teacher's best-response search")
+    ap.add_argument("--eval-every", type=int, default=0)
+    ap.add_argument("--eval-scenes", type=int, default=1024)
+    ap.add_argument("--eval-seed", type=int, default=1)
+    a = ap.parse_args(argv)
+    run = ImitationRun(a.envs, a.uavs, a.targets, a.minibatch, a.out, seed=a.seed, epochs=a.epochs,
+                       eval_every=a.eval_every, eval_scenes=a.eval_scenes, eval_seed=a.eval_seed,
+                       max_sweeps=a.max_sweeps, assign_weight=a.assign_weight)
+    print(json.dumps(run.fit(a.iterations)))
+
+
+if __name__ == "__main__":
+    main()

@@ -278,6 +278,54 @@ class VecUAVEnv:
                                             ptr(covered), ptr(stats), stream_handle()), "uavhip_refine_assignments")
         return out, J, covered, stats
 
+    def teacher_steps(self, assignment, n_max=None, obs=None, actions=None, reward=None, done=None, info=None,
+                      steps=None, finished=None, ep_return=None, stats=None, want_info=False):
+        """uavhip_teacher_steps: walk every env from its current state (reset it first) along
+        `assignment` [E, N] int32 target ids or -1 (refine_assignments' / select_best's format), at
+        most n_max steps (default N * M, which bounds every episode), the action of each step derived
+        from the pointer: 1 iff the pointer's target is the pointer's UAV's teacher target.
+        Returns a dict of time-major device tensors: obs [n_max, E, 5, 14] f32 (obs[t] = the window
+        step t's action was decided on), actions [n_max, E] int8 (-1 at or past an env's end),
+        reward [n_max, E] f64, done [n_max, E] u8, info [n_max, E, INFO_COUNT] f64 (want_info or a given
+        buffer, else None), steps [E] int32 and ep_return [E] f64 (ADDED to when given, else from
+        zero), finished [E] u8, stats [E, 2] int32 (rejected teacher assigns, invalid ids). Buffers
+        given are used as they are; the rest are allocated. The env is stepped."""
+        if self.obs_dtype != torch.float32:
+            raise TypeError("teacher_steps: f32 observations only (this env emits float16)")
+        n_max = self.N * self.M if n_max is None else int(n_max)
+        if n_max < 1:
+            raise ValueError(f"teacher_steps: n_max={n_max} must be >= 1")
+        if assignment is None:
+            raise ValueError("teacher_steps: assignment is required ([E, N] int32 target ids or -1)")
+        E, dev = self.E, self.device
+        lead = (n_max, E)
+        f64 = dict(dtype=torch.float64, device=dev)
+        obs = torch.empty(*lead, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev) if obs is None else obs
+        actions = torch.empty(*lead, dtype=torch.int8, device=dev) if actions is None else actions
+        reward = torch.empty(*lead, **f64) if reward is None else reward
+        done = torch.empty(*lead, dtype=torch.uint8, device=dev) if done is None else done
+        if info is None and want_info:
+            info = torch.empty(*lead, _lib.INFO_COUNT, **f64)
+        steps = torch.zeros(E, dtype=torch.int32, device=dev) if steps is None else steps
+        finished = torch.zeros(E, dtype=torch.uint8, device=dev) if finished is None else finished
+        ep_return = torch.zeros(E, **f64) if ep_return is None else ep_return
+        stats = torch.empty(E, 2, dtype=torch.int32, device=dev) if stats is None else stats
+        check_out(assignment, "assignment", torch.int32, (E, self.N), dev)
+        check_out(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
+        check_out(actions, "actions", torch.int8, lead, dev)
+        check_out(reward, "reward", torch.float64, lead, dev)
+        check_out(done, "done", torch.uint8, lead, dev)
+        check_out(info, "info", torch.float64, lead, dev, (_lib.INFO_COUNT,))
+        check_out(steps, "steps", torch.int32, (E,), dev)
+        check_out(finished, "finished", torch.uint8, (E,), dev)
+        check_out(ep_return, "ep_return", torch.float64, (E,), dev)
+        check_out(stats, "stats", torch.int32, (E, 2), dev)
+        check(LIB.uavhip_teacher_steps(self.desc, ptr(assignment), n_max, ptr(obs), ptr(actions), ptr(reward),
+                                       ptr(done), ptr(info), ptr(steps), ptr(finished), ptr(ep_return), ptr(stats),
+                                       stream_handle()), "uavhip_teacher_steps")
+        return dict(obs=obs, actions=actions, reward=reward, done=done, info=info, steps=steps, finished=finished,
+                    ep_return=ep_return, stats=stats)
+
     def episodes(self):
         return self.istate[:, _lib.IST["EPISODE"]]
 
