@@ -481,6 +481,43 @@ int uavhip_teacher_steps(const uavhip_env* env, const int32_t* assignment, int32
                          int8_t* actions, double* reward, uint8_t* done, double* info, int32_t* steps,
                          uint8_t* finished, double* ep_return, int32_t* stats, uavhip_stream_t stream);
 
+/* On-policy expert labels (k_expert_steps, expert.hip): walk every env along an ARBITRARY action
+ * trace, up to n_max steps in ONE launch, and record per step the window the action was decided on,
+ * the action taken and what the state-wise expert would have done in that state -- the relabelling
+ * step of DAgger (uavhip.imitate, source "dagger"). The expert at the env's pointer (u, t), with
+ * list-order targets t' = 0..M-1, v = tgt_value, c = uav_cost, w = prm[UAVHIP_PRM_OMEGA]:
+ *   P[x][t'] = p_dmg[x][t'] * p_pen[x]                                  (the env step's pf);
+ *   Q[t']    = the product of (1.0 - P[x][t']) over the UAVs x currently locked on t', ascending x,
+ *              from 1.0 (the env's nh_final[t'] is that product bit for bit: the walk locks UAVs in
+ *              ascending order, at most once each);
+ *   g[t']    = (v[t'] * Q[t']) * P[u][t'] - (w * c[u])   in that order of operations, not contracted;
+ *   label    = 1 iff g[t] > 0.0 and g[t'] <= g[t] for every t < t' < M, else 0;
+ *   margin   = g[t] - max(0.0, max_{t' > t} g[t'])       (the inner max over nothing counts as 0.0).
+ * g[t'] is u's marginal contribution to J (uavhip_refine_assignments) on the targets the walk can
+ * still reach; following the labels from a reset is one best-response sweep from the empty
+ * assignment: the allocation of uavhip_refine_assignments(NULL, max_sweeps = 1).
+ *  - the action taken: env e follows the expert (action = label) iff actions_in == NULL or
+ *    (follow != NULL and follow[e] != 0); otherwise it takes actions_in[step][e] (actions_in
+ *    [n_max][E] int8, follow [E] u8; follow without actions_in is refused). A value outside {0, 1}
+ *    on a live env ends its trace: the env is held from that step on, finished[e] stays 0 and
+ *    stats[e][2] = 1 (an env that has finished ignores its trace: uavhip_decode_steps' -1 rows);
+ *  - the step is the env step with UAVHIP_STEP_HOLD, bitwise uavhip_env_step's for the same action;
+ *    every env starts from its CURRENT state, an env already finished is held from step 0;
+ *  - outputs, time-major, each nullable: obs [n_max][E][5][14] f32 (obs[t] = the window step t's
+ *    action was decided on, uavhip_teacher_steps' convention); actions [n_max][E] int8 (the action
+ *    taken); labels [n_max][E] int8; margin [n_max][E] f64; reward [n_max][E] f64; done [n_max][E]
+ *    u8. Held rows (at or past the env's end, or past its trace's end): a zero window, action -1,
+ *    label -1, margin 0, reward 0, done 1;
+ *  - steps [E] int32 (required): ADDED to; finished [E] u8 (required): written; ep_return [E] f64
+ *    (nullable): the rewards ADDED to it in step order -- as uavhip_teacher_steps;
+ *  - stats [E][3] int32 (nullable), written: assigns the env rejected in this call, steps whose
+ *    action differs from the label, 1 if the trace ended on a live env else 0.
+ * Needs n_max >= 1. The full N <= 64, M <= 128 range; f32 observations only (UAVHIP_EINVAL under
+ * UAVHIP_ENV_OBS_F16). */
+int uavhip_expert_steps(const uavhip_env* env, const int8_t* actions_in, const uint8_t* follow, int32_t n_max,
+                        float* obs, int8_t* actions, int8_t* labels, double* margin, double* reward, uint8_t* done,
+                        int32_t* steps, uint8_t* finished, double* ep_return, int32_t* stats, uavhip_stream_t stream);
+
 /* ---------------------------------------------------------------- PPO update (K5) */
 
 /* One clipped-PPO minibatch step of agents/ppo.py:96-169 (evaluate -> surrogate / clipped value

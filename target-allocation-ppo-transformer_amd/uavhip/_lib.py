@@ -121,6 +121,8 @@ _SIGS = {
                                                  _vp]),
     "uavhip_teacher_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
+    "uavhip_expert_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp]),
     "uavhip_ppo_workspace_floats": (ctypes.c_int64, [_i32]),
     "uavhip_ppo_step": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "uavhip_ppo_diagnostics_partials": (_i32, [ctypes.c_int64]),

@@ -7,6 +7,7 @@ policy, from teacher-forced episodes.
 
     python -m uavhip.imitate --envs 4096 --uavs 16 --targets 32 --minibatch 4096 --iterations 20 --out runs/clone
     python -m uavhip.fit ... --init runs/clone/final_model.pth
+    python -m uavhip.imitate ... --source dagger --expert-share 0.25 --assign-weight 16
 
 One iteration: fresh on-device scenes, the teacher allocation of every scene
 (VecUAVEnv.refine_assignments from the empty assignment: AllocationSolver.baseline's search), ONE
@@ -26,17 +27,41 @@ TransformerActorCritic(); iteration i = 1, 2, .. draws its scenes with env.desc.
 AllocationSolver._generate_scenes sets it) after zeroing istate; minibatch orders from
 torch.Generator().manual_seed(seed), continuing across iterations: torch.randperm(rows) per epoch.
 Same seed, same parameters, bit for bit. An ImitationRun cannot be resumed.
+
+source = "expert" | "dagger" (ImitationRun(source=...), --source; "teacher", the path above, is the
+default) take the labels from uavhip_expert_steps instead: the state-wise expert's action at every
+state an env visits (include/uavhip.h has the rule; followed from a reset it is one best-response
+sweep from the empty assignment). "expert": every env follows the expert, the labels are the actions
+-- the teacher path with the other label definition. "dagger": iteration 1 runs as "expert"; from
+iteration 2 the states are the LEARNER's own -- the scenes are generated as above, then
+    env.reset(episode=1, obs_out=obs2[0]); steps.zero_()
+    policy.decode_steps(env, obs2, rowproj, 0, True, steps, finished, actions=trace, n_max=N * M,
+                        greedy_stride=0, seed=seed + i, offset=0, offset_stride=E)     # sampled
+    expert_batch(env, trace, follow)       # env.reset(), then ONE uavhip_expert_steps(trace, follow)
+with follow[e] = 1 for e < ceil(expert_share * E) (those envs follow the expert instead of their
+trace, so expert episodes stay in every batch), and imitation_update fits the policy to the LABELS
+on every valid row, assign_weight on the label-1 rows. Rows are not aggregated across iterations.
+obs2, rowproj, steps, finished, trace and follow are the run's own buffers. The decode kernel needs
+N, M <= 64, so "dagger" refuses more; "expert" does not. The contract above holds unchanged: the
+decode draws from Philox counters keyed by seed + i, nothing from a torch generator, so two runs with
+one seed end bitwise equal. progress.jsonl gains, for these two sources, label_agreement (the share
+of the learner's rows -- the envs that do not follow -- whose action taken equals the label),
+assign_agreement (that share over the learner's label-1 rows; null without such rows, as in
+iteration 1 -- the update's own figure, the greedy action after the update on every label-1 row, is
+fit_assign_agreement there) and rejected_assigns (assigns the env rejected, all envs).
 """
 import json
 import os
 import time
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
 from .config import cfg
 
 PROGRESS_FIELDS = ("iteration", "rows", "nll_before", "nll_after", "agreement", "teacher_mean_J", "rejected")
+SOURCES = ("teacher", "expert", "dagger")
 EVAL_FIELDS = ("eval_mean_J", "eval_mean_J_baseline", "eval_beats_baseline")
 
 
@@ -71,6 +96,54 @@ def teacher_batch(env, assignment=None, max_sweeps=32, gamma=None):
     rows = torch.nonzero(out["actions"].reshape(-1) >= 0).reshape(-1).to(torch.int32)
     return TeacherBatch(out["obs"], out["actions"], returns, rows, out["steps"],
                         env.dstate[:, _lib.DST["J"]].clone(), teacher_J, out["stats"][:, 0].clone())
+
+
+@dataclass
+class ExpertBatch:
+    """uavhip_expert_steps' episodes in TeacherBatch's layout: `actions` are the expert's LABELS
+    (what imitation_update fits), `taken` the actions the envs took."""
+    obs: torch.Tensor        # [n_max, E, 5, 14] f32: obs[t] is the window step t's action was decided on
+    actions: torch.Tensor    # [n_max, E] int8: the expert's label, -1 in held rows
+    returns: torch.Tensor    # [n_max, E] f32: discounted return-to-go of the walked episode, 0 in held rows
+    rows: torch.Tensor       # [rows] int32: flat indices (t * E + e) of the valid rows, ascending
+    steps: torch.Tensor      # [E] int32: episode lengths
+    J: torch.Tensor          # [E] f64: J of the allocation the env ended on (dstate[J])
+    teacher_J: torch.Tensor  # [E] f64: J of the one-sweep expert's allocation (refine_assignments(None, max_sweeps=1))
+    rejected: torch.Tensor   # [E] int32: assigns the env rejected
+    taken: torch.Tensor      # [n_max, E] int8: the action taken, -1 in held rows
+    margin: torch.Tensor     # [n_max, E] f64: the label's margin, 0 in held rows
+    stats: torch.Tensor      # [E, 3] int32: rejected assigns, steps with action != label, trace ended
+    follow: Optional[torch.Tensor]  # [E] u8 as passed: the envs that followed the expert (None: all)
+
+
+@torch.no_grad()
+def expert_batch(env, actions=None, follow=None, gamma=None):
+    """Reset `env`, walk it along the trace `actions` ([N * M, E] int8; None: every env follows the
+    expert; follow [E] u8: the envs that do so anyway) in one uavhip_expert_steps launch of N * M
+    steps, and return the episodes with the expert's label of every step as an ExpertBatch. returns
+    as teacher_batch's, from the walked episode's rewards."""
+    from . import _lib
+    from .ppo import gae
+    env.reset()
+    _, expert_J, _, _ = env.refine_assignments(None, max_sweeps=1)
+    out = env.expert_steps(actions, follow, n_max=env.N * env.M)
+    returns, _, _ = gae(out["reward"], out["done"], torch.zeros_like(out["reward"], dtype=torch.float32),
+                        gamma=cfg.GAMMA if gamma is None else gamma, lam=1.0, normalize=False)
+    rows = torch.nonzero(out["labels"].reshape(-1) >= 0).reshape(-1).to(torch.int32)
+    return ExpertBatch(out["obs"], out["labels"], returns, rows, out["steps"], env.dstate[:, _lib.DST["J"]].clone(),
+                       expert_J, out["stats"][:, 0].clone(), out["actions"], out["margin"], out["stats"], follow)
+
+
+def learner_agreement(batch):
+    """(label_agreement, assign_agreement) of an ExpertBatch over the learner's rows (the envs that
+    did not follow the expert): the share of rows whose action taken equals the label, and that share
+    over the label-1 rows; NaN without such rows."""
+    E = batch.steps.numel()
+    learner = torch.zeros(E, dtype=torch.bool, device=batch.steps.device) if batch.follow is None else batch.follow == 0
+    rows = (batch.actions >= 0) & learner[None, :]
+    hit = (batch.taken == batch.actions)
+    q = torch.stack([hit[rows].double().mean(), hit[rows & (batch.actions == 1)].double().mean()]).tolist()
+    return q[0], q[1]
 
 
 def _forward(policy, states, actions):
@@ -145,7 +218,7 @@ def imitation_update(trainer, policy, batch, epochs, generator, assign_weight=1.
             "assign_agreement": q[4], "optimizer_steps": int(cnt)}
 
 
-def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0):
+def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0, source="teacher", expert_share=0.25):
     """ImitationRun's argument checks that need no device; each message names the argument."""
     if minibatch <= 0 or minibatch % 64:
         raise ValueError(f"minibatch={minibatch}: must be a positive multiple of 64 (the training step's tile)")
@@ -160,17 +233,30 @@ def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0):
     if eval_every > 0 and (uavs > 64 or targets > 64):
         raise ValueError(f"eval_every={eval_every}: the evaluation decodes with N, M <= 64 "
                          f"(uavs={uavs}, targets={targets}); pass eval_every=0")
+    if source not in SOURCES:
+        raise ValueError(f"source={source!r}: must be one of {', '.join(SOURCES)}")
+    if source == "dagger" and (uavs > 64 or targets > 64):
+        raise ValueError(f"source='dagger': the learner's trace comes from the decode kernel, which needs N, M <= 64 "
+                         f"(uavs={uavs}, targets={targets}); source='expert' has no such limit")
+    if not 0.0 <= expert_share <= 1.0:
+        raise ValueError(f"expert_share={expert_share}: must be in [0, 1]")
 
 
 class ImitationRun:
     def __init__(self, envs, uavs, targets, minibatch, out_dir, seed=0, epochs=None, eval_every=0, eval_scenes=1024,
                  eval_seed=1, max_sweeps=32, assign_weight=1.0, lr_actor=None, lr_critic=None, eps_clip=None,
-                 max_grad_norm=None, value_coef=0.5, entropy_coef=0.01, device="cuda:0"):
+                 max_grad_norm=None, value_coef=0.5, entropy_coef=0.01, device="cuda:0", source="teacher",
+                 expert_share=0.25):
+        """source: "teacher" (the baseline's episodes), "expert" (the state-wise expert's own walk) or
+        "dagger" (the learner's sampled walk, relabelled by the expert; module docstring).
+        expert_share: under "dagger", the share of envs that follow the expert instead."""
         self.E, self.N, self.M = int(envs), int(uavs), int(targets)
         self.minibatch = int(minibatch)
         self.epochs = int(cfg.K_EPOCHS if epochs is None else epochs)
         self.eval_every = int(eval_every)
-        validate_args(self.E, self.N, self.M, self.minibatch, self.epochs, self.eval_every)
+        self.source, self.expert_share = source, float(expert_share)
+        validate_args(self.E, self.N, self.M, self.minibatch, self.epochs, self.eval_every, self.source,
+                      self.expert_share)
         self.eval_scenes, self.eval_seed = int(eval_scenes), int(eval_seed)
         self.max_sweeps, self.assign_weight = int(max_sweeps), float(assign_weight)
         self.seed = int(seed)
@@ -195,6 +281,8 @@ class ImitationRun:
         self.last = None
         self.solver = None
         self.baseline_J = None
+        self.batch = None  # "expert" / "dagger": the last iteration's ExpertBatch
+        self.trace = None  # "dagger": the decode buffers, made at iteration 2
 
     def _evaluate(self):
         from .solve import AllocationSolver
@@ -205,6 +293,31 @@ class ImitationRun:
         return {"eval_mean_J": float(J.mean()), "eval_mean_J_baseline": float(self.baseline_J.mean()),
                 "eval_beats_baseline": float((J > self.baseline_J).double().mean())}
 
+    @torch.no_grad()
+    def learner_trace(self):
+        """The learner's sampled walk over the env's current scenes (module docstring): (trace
+        [N * M, E] int8, -1 past an env's end; follow [E] u8). The env is left at the walk's end."""
+        import math
+
+        from . import _lib
+        from .policy import rowproj_buffer
+        env, E, dev = self.env, self.E, self.device
+        if self.trace is None:
+            self.obs2 = torch.zeros(2, E, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev)
+            self.rowproj = rowproj_buffer(E, dev)
+            self.steps = torch.zeros(E, dtype=torch.int32, device=dev)
+            self.finished = torch.zeros(E, dtype=torch.uint8, device=dev)
+            self.trace = torch.empty(self.N * self.M, E, dtype=torch.int8, device=dev)
+            self.follow = torch.zeros(E, dtype=torch.uint8, device=dev)
+            self.follow[:math.ceil(self.expert_share * E)] = 1
+        env.reset(episode=1, obs_out=self.obs2[0])
+        self.steps.zero_()
+        self.policy.packed_weights()
+        self.policy.decode_steps(env, self.obs2, self.rowproj, 0, True, self.steps, self.finished, actions=self.trace,
+                                 n_max=self.N * self.M, greedy_stride=0,
+                                 seed=(self.seed + self.iteration) & (2 ** 64 - 1), offset=0, offset_stride=E)
+        return self.trace, self.follow
+
     def step(self):
         """One iteration; returns the progress line's fields (also appended to progress.jsonl)."""
         from .fit import progress_line
@@ -214,13 +327,22 @@ class ImitationRun:
         env.desc.seed = (self.seed + it) & (2 ** 64 - 1)
         env.istate.zero_()
         env.generate_scenes()
-        batch = teacher_batch(env, None, max_sweeps=self.max_sweeps)
+        if self.source == "teacher":
+            batch = teacher_batch(env, None, max_sweeps=self.max_sweeps)
+        else:
+            self.batch = None  # run.batch is the last ExpertBatch; released before the next is made
+            learner = self.source == "dagger" and it >= 2
+            self.batch = batch = expert_batch(env, *(self.learner_trace() if learner else ()))
         q = imitation_update(self.trainer, self.policy, batch, self.epochs, self.generator, self.assign_weight)
         f = {"iteration": it, "rows": q["rows"], "nll_before": q["nll_before"], "nll_after": q["nll_after"],
              "agreement": q["agreement"], "teacher_mean_J": float(batch.teacher_J.mean()),
              "rejected": int(batch.rejected.sum()), "agreement_before": q["agreement_before"],
              "assign_agreement": q["assign_agreement"], "assign_share": float((batch.actions == 1).sum()) / q["rows"],
              "walked_mean_J": float(batch.J.mean()), "optimizer_steps": q["optimizer_steps"]}
+        if self.source != "teacher":
+            f["label_agreement"], f["assign_agreement"] = learner_agreement(batch)
+            f.update(fit_assign_agreement=q["assign_agreement"], rejected_assigns=int(batch.rejected.sum()),
+                     trace_ended=int(batch.stats[:, 2].sum()), source=self.source)
         if self.eval_every > 0 and it % self.eval_every == 0:
             f.update(self._evaluate())
         self.wall_s += time.perf_counter() - t0
@@ -261,10 +383,16 @@ def main(argv=None):
     ap.add_argument("--eval-every", type=int, default=0)
     ap.add_argument("--eval-scenes", type=int, default=1024)
     ap.add_argument("--eval-seed", type=int, default=1)
+    ap.add_argument("--source", choices=SOURCES, default="teacher",
+                    help="teacher: the baseline's episodes; expert: the state-wise expert's own walk; dagger: the "
+                         "learner's sampled walk relabelled by the expert")
+    ap.add_argument("--expert-share", type=float, default=0.25,
+                    help="dagger: the share of envs that follow the expert instead of the learner's trace")
     a = ap.parse_args(argv)
     run = ImitationRun(a.envs, a.uavs, a.targets, a.minibatch, a.out, seed=a.seed, epochs=a.epochs,
                        eval_every=a.eval_every, eval_scenes=a.eval_scenes, eval_seed=a.eval_seed,
-                       max_sweeps=a.max_sweeps, assign_weight=a.assign_weight)
+                       max_sweeps=a.max_sweeps, assign_weight=a.assign_weight, source=a.source,
+                       expert_share=a.expert_share)
     print(json.dumps(run.fit(a.iterations)))
 
 

@@ -326,6 +326,62 @@ class VecUAVEnv:
         return dict(obs=obs, actions=actions, reward=reward, done=done, info=info, steps=steps, finished=finished,
                     ep_return=ep_return, stats=stats)
 
+    def expert_steps(self, actions=None, follow=None, n_max=None, obs=None, actions_out=None, labels=None, margin=None,
+                     reward=None, done=None, steps=None, finished=None, ep_return=None, stats=None):
+        """uavhip_expert_steps: walk every env from its current state (reset it first) along the
+        action trace `actions` [n_max, E] int8 (a learner's own, e.g. decode_steps' trace; None: every
+        env follows the expert) and label every step with the state-wise expert's action there
+        (include/uavhip.h has the rule). follow [E] u8 (needs `actions`): the envs that follow the
+        expert instead of their trace. n_max defaults to the trace's length, else N * M.
+        Returns a dict of time-major device tensors: obs [n_max, E, 5, 14] f32 (obs[t] = the window
+        step t's action was decided on), actions [n_max, E] int8 (the action taken), labels [n_max, E]
+        int8, margin [n_max, E] f64, reward [n_max, E] f64, done [n_max, E] u8 -- held rows: a zero
+        window, action -1, label -1, margin 0, reward 0, done 1 --, steps [E] int32 and ep_return [E]
+        f64 (ADDED to when given, else from zero), finished [E] u8, stats [E, 3] int32 (assigns the
+        env rejected, steps with action != label, 1 if the trace ended on a live env). Buffers given
+        are used as they are; the rest are allocated. The env is stepped."""
+        if self.obs_dtype != torch.float32:
+            raise TypeError("expert_steps: f32 observations only (this env emits float16)")
+        E, dev = self.E, self.device
+        if follow is not None and actions is None:
+            raise ValueError("expert_steps: follow needs actions (without a trace every env follows the expert)")
+        if actions is not None and (not isinstance(actions, torch.Tensor) or actions.dim() != 2):
+            raise ValueError("expert_steps: actions must be an [n_max, E] int8 tensor")
+        if n_max is None:
+            n_max = self.N * self.M if actions is None else int(actions.shape[0])
+        n_max = int(n_max)
+        if n_max < 1:
+            raise ValueError(f"expert_steps: n_max={n_max} must be >= 1")
+        lead = (n_max, E)
+        f64 = dict(dtype=torch.float64, device=dev)
+        check_out(actions, "actions", torch.int8, lead, dev)
+        check_out(follow, "follow", torch.uint8, (E,), dev)
+        obs = torch.empty(*lead, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev) if obs is None else obs
+        actions_out = torch.empty(*lead, dtype=torch.int8, device=dev) if actions_out is None else actions_out
+        labels = torch.empty(*lead, dtype=torch.int8, device=dev) if labels is None else labels
+        margin = torch.empty(*lead, **f64) if margin is None else margin
+        reward = torch.empty(*lead, **f64) if reward is None else reward
+        done = torch.empty(*lead, dtype=torch.uint8, device=dev) if done is None else done
+        steps = torch.zeros(E, dtype=torch.int32, device=dev) if steps is None else steps
+        finished = torch.zeros(E, dtype=torch.uint8, device=dev) if finished is None else finished
+        ep_return = torch.zeros(E, **f64) if ep_return is None else ep_return
+        stats = torch.empty(E, 3, dtype=torch.int32, device=dev) if stats is None else stats
+        check_out(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
+        check_out(actions_out, "actions_out", torch.int8, lead, dev)
+        check_out(labels, "labels", torch.int8, lead, dev)
+        check_out(margin, "margin", torch.float64, lead, dev)
+        check_out(reward, "reward", torch.float64, lead, dev)
+        check_out(done, "done", torch.uint8, lead, dev)
+        check_out(steps, "steps", torch.int32, (E,), dev)
+        check_out(finished, "finished", torch.uint8, (E,), dev)
+        check_out(ep_return, "ep_return", torch.float64, (E,), dev)
+        check_out(stats, "stats", torch.int32, (E, 3), dev)
+        check(LIB.uavhip_expert_steps(self.desc, ptr(actions), ptr(follow), n_max, ptr(obs), ptr(actions_out),
+                                      ptr(labels), ptr(margin), ptr(reward), ptr(done), ptr(steps), ptr(finished),
+                                      ptr(ep_return), ptr(stats), stream_handle()), "uavhip_expert_steps")
+        return dict(obs=obs, actions=actions_out, labels=labels, margin=margin, reward=reward, done=done, steps=steps,
+                    finished=finished, ep_return=ep_return, stats=stats)
+
     def episodes(self):
         return self.istate[:, _lib.IST["EPISODE"]]
 
