@@ -550,6 +550,8 @@ typedef struct uavhip_ppo {
        rounding per element (train.hip k_adam) */
     double lr_actor, lr_critic, beta1, beta2, adam_eps; /* 2e-4, 1e-3, 0.9, 0.999, 1e-8 */
     float eps_clip, max_grad_norm, value_coef, entropy_coef; /* 0.2, 1.0, 0.5, 0.01 */
+    int32_t flags;       /* UAVHIP_PPO_* variant bits below (0 = the measured defaults); any other
+                            bit is UAVHIP_EINVAL. The workspace size does not depend on them */
 } uavhip_ppo;
 
 /* uavhip_ppo_step phases (bit mask). A data-parallel step over R ranks runs FORWARD,
@@ -563,6 +565,24 @@ enum uavhip_ppo_phase {
     UAVHIP_PPO_PACKED = 8    /* with FORWARD: the workspace's packed weight copies are current (an
                                 UPDATE on this workspace refreshes them with the new parameters,
                                 and nothing changed the parameters since): skip the repack */
+};
+
+/* uavhip_ppo.flags (bit mask): each bit forces the other of two kernel paths that compute the same
+ * step, for comparisons and traces. 0 is the measured default everywhere. */
+enum uavhip_ppo_flag {
+    UAVHIP_PPO_NO_POS_SPLIT = 1,     /* the 16-samples-per-workgroup forward / backward (K6) even at the
+                                        minibatches that run the position split (K7) by default (0)   */
+    UAVHIP_PPO_NO_TRUNK_SPLIT = 2,   /* actor and critic trunk in the same workgroups even at the
+                                        minibatches that run them side by side by default (0)         */
+    UAVHIP_PPO_WGRAD_STREAM_K = 4,   /* the stream-K weight-gradient schedule at every size; default
+                                        (0): chunked from 64 k-slabs (2048 rows) on                   */
+    UAVHIP_PPO_FIXED_ORDER_FWD = 8,  /* every workgroup of the training forward runs the actor trunk
+                                        first; default (0): the order mixed across workgroups         */
+    UAVHIP_PPO_FIXED_ORDER_BWD = 16, /* every workgroup of the backward runs the critic trunk first;
+                                        default (0): the order mixed across workgroups                */
+    UAVHIP_PPO_NO_GRAD_PRESCALE = 32,/* the backward without its power-of-two gradient pre-scale;
+                                        default (0): scaled by the power of two >= global_minibatch   */
+    UAVHIP_PPO_FLAGS_ALL = 63
 };
 
 /* Floats of workspace one step needs at `minibatch` samples. */
@@ -664,7 +684,8 @@ int uavhip_copy_async(void* dst, const void* src, uint64_t bytes, uavhip_stream_
 const char* uavhip_last_error(void);
 /* 4 since round 3 (struct uavhip_ppo: the Adam hyper-parameters are doubles; the inference packed
    buffer carries split weight copies, uavhip_policy_split_layout); 5 since round 5 (the packed
-   buffer ends with the range table, uavhip_policy_range_table; N > 1 peers by PCI bus id); the
+   buffer ends with the range table, uavhip_policy_range_table; N > 1 peers by PCI bus id); 6: struct
+   uavhip_ppo ends with `flags`, and the update step reads no environment variable any more; the
    ctypes binding refuses a library of another version */
 int32_t uavhip_abi_version(void);
 

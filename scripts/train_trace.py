@@ -9,11 +9,6 @@ import sys
 
 import numpy as np
 
-# one trunk order in every workgroup, so "cycles since block start" medians line up phase by phase
-# (TrainIO::mix / BwdIO::mix run half the workgroups in the other order)
-os.environ.setdefault("UAVHIP_FWD_MIX", "0")
-os.environ.setdefault("UAVHIP_BWD_MIX", "0")
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "target-allocation-ppo-transformer_amd"))
 import torch  # noqa: E402
@@ -42,7 +37,10 @@ vals = torch.randn(n, generator=g).to(dev)
 ret = vals + 0.3 * torch.randn(n, generator=g).to(dev)
 adv = torch.randn(n, generator=g).to(dev)
 torch.manual_seed(0)
-tr = FusedPPOTrainer(TransformerActorCritic().to(dev), bs)
+# one trunk order in every workgroup, so "cycles since block start" medians line up phase by phase
+# (TrainIO::mix / BwdIO::mix run half the workgroups in the other order)
+tr = FusedPPOTrainer(TransformerActorCritic().to(dev), bs,
+                     flags=_lib.PPO_FIXED_ORDER_FWD | _lib.PPO_FIXED_ORDER_BWD)
 tr.set_buffers(states, acts, logp, vals, ret, adv)
 tr.run(epochs=1, generator=torch.Generator().manual_seed(1), use_graph=False)
 torch.cuda.synchronize()

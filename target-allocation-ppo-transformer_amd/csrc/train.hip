@@ -21,7 +21,6 @@
 // all rows, everything else for Bm rows (compact [Bm][...] tensors), so its gradients are exactly
 // the dense model's.
 #include <cmath>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "policy_layout.hpp"
@@ -484,8 +483,8 @@ inline Plan make_plan(int Bm, float* base) {
     p.Bm = Bm;
     p.R = Bm * S;
     const int R = p.R;
-    // partial rows: sized for the position split whenever this minibatch may run it (independent
-    // of UAVHIP_POS_SPLIT, so the workspace size never depends on the environment)
+    // partial rows (and kvc below): sized for the position split whenever this minibatch size can
+    // run it, whether or not uavhip_ppo.flags turns it off, so the workspace size never depends on the flags
     p.prows = (pol::ps_capable(Bm) ? S : 1) * (Bm / kHeadSamples);
     p.xg = w.take((size_t)R * 16);
     p.mask = w.take(R);
@@ -522,11 +521,12 @@ inline Plan make_plan(int Bm, float* base) {
 }
 
 
+// The variant choices below read uavhip_ppo.flags (include/uavhip.h): 0 takes the measured default.
+
 // The backward's gradient pre-scale (BwdIO::gscale): the power of two >= the global minibatch
-// (UAVHIP_GRAD_PRESCALE=0: 1, the unscaled backward, for the per-element precision test's A/B).
-inline float grad_prescale(int Bg) {
-    const char* e = std::getenv("UAVHIP_GRAD_PRESCALE");
-    if (e && e[0] == '0') return 1.0f;
+// (UAVHIP_PPO_NO_GRAD_PRESCALE: 1, the unscaled backward, for the per-element precision test's A/B).
+inline float grad_prescale(int flags, int Bg) {
+    if (flags & UAVHIP_PPO_NO_GRAD_PRESCALE) return 1.0f;
     int s = 1;
     while (s < Bg && s < (1 << 30)) s <<= 1;
     return (float)s;
@@ -535,61 +535,20 @@ inline float grad_prescale(int Bg) {
 inline const float* prm(const uavhip_ppo* c, int i) { return c->params + kOffs.o[i]; }
 inline AdamHyper adam_hyper(const uavhip_ppo* c) { return AdamHyper{c->lr_actor, c->lr_critic, c->beta1, c->beta2}; }
 
-// Position split (K7) for this minibatch size (UAVHIP_POS_SPLIT=0 turns it off: tests compare both ways).
-inline bool pos_split(int Bm) {
-    const char* e = std::getenv("UAVHIP_POS_SPLIT");
-    return pol::ps_capable(Bm) && !(e && e[0] == '0');
-}
-
-// Weight gradients in direct mode (WgBatch::direct) only on request (UAVHIP_WGRAD_DIRECT=1, and
-// only when no tile has more than kWgDirectMaxSlabs slabs): measured at minibatch 64 (r04b, same box,
-// scripts/train_probe.py) the stream-K form with k_reduce_grads is faster, 0.098 against 0.113 ms
-// per step -- one workgroup walking a tile's 10 slabs is a longer chain than spreading them over
-// 148 workgroups and summing the partials.
-inline bool wgrad_direct(int max_slabs) {
-    const char* e = std::getenv("UAVHIP_WGRAD_DIRECT");
-    return e && e[0] == '1' && max_slabs <= kWgDirectMaxSlabs;
-}
+// Position split (K7) for this minibatch size (UAVHIP_PPO_NO_POS_SPLIT turns it off).
+inline bool pos_split(int flags, int Bm) { return pol::ps_capable(Bm) && !(flags & UAVHIP_PPO_NO_POS_SPLIT); }
 
 // Weight gradients in chunked mode (WgBatch::chunk: one (chunk, tile) per workgroup, operand-sharing
-// tiles on one XCD) for long k ranges (>= 64 slabs: 2048 rows); UAVHIP_WGRAD_CHUNK=0 / 1 forces
-// stream-K / chunked.
-inline bool wgrad_chunked(int max_slabs) {
-    const char* e = std::getenv("UAVHIP_WGRAD_CHUNK");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-    return max_slabs >= 64;
+// tiles on one XCD) for long k ranges (>= 64 slabs: 2048 rows); UAVHIP_PPO_WGRAD_STREAM_K: never.
+// Walking a whole tile in one workgroup with no partial reduction ("direct mode") was tried for the
+// short ranges and removed: 0.113 against stream-K's 0.098 ms per step at minibatch 64.
+inline bool wgrad_chunked(int flags, int max_slabs) {
+    return max_slabs >= 64 && !(flags & UAVHIP_PPO_WGRAD_STREAM_K);
 }
 
-// K6's trunk order mixed across workgroups (BwdIO::mix; UAVHIP_BWD_MIX=0: every workgroup critic first)
-inline int bwd_mix() {
-    const char* e = std::getenv("UAVHIP_BWD_MIX");
-    return !(e && e[0] == '0');
-}
-
-// The training forward's trunk order mixed across workgroups (TrainIO::mix; UAVHIP_FWD_MIX=0: actor first)
-inline int fwd_mix() {
-    const char* e = std::getenv("UAVHIP_FWD_MIX");
-    return !(e && e[0] == '0');
-}
-
-// Chunk length of the three-plane problems relative to the two-plane ones in the chunked schedule
-// (UAVHIP_WGRAD_P3_RATIO, default 0.75: the per-slab cost ratio of the two forms)
-inline float wgrad_p3_ratio() {
-    const char* e = std::getenv("UAVHIP_WGRAD_P3_RATIO");
-    const float r = e ? (float)std::atof(e) : 0.75f;
-    return r > 0.f && r <= 1.f ? r : 0.75f;
-}
-
-// Every weight-gradient tile on three-plane products (UAVHIP_WGRAD_PLANES=3; default: the key rows only)
-inline bool wgrad_all_three_planes() {
-    const char* e = std::getenv("UAVHIP_WGRAD_PLANES");
-    return e && e[0] == '3';
-}
-
-// Trunk split for this minibatch size (UAVHIP_TRUNK_SPLIT=0 turns it off: tests compare both ways).
-inline int split_blocks(int Bm) {
-    const char* e = std::getenv("UAVHIP_TRUNK_SPLIT");
-    return (pol::trunk_split(Bm) && !(e && e[0] == '0')) ? Bm / kHeadSamples : 0;
+// Trunk split for this minibatch size (UAVHIP_PPO_NO_TRUNK_SPLIT turns it off).
+inline int split_blocks(int flags, int Bm) {
+    return (pol::trunk_split(Bm) && !(flags & UAVHIP_PPO_NO_TRUNK_SPLIT)) ? Bm / kHeadSamples : 0;
 }
 
 }  // namespace tr
@@ -637,6 +596,11 @@ extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const i
                   c->minibatch, Bg, c->n_floats, kOffs.o[kNumParams], phases);
         return UAVHIP_EINVAL;
     }
+    if (c->flags & ~UAVHIP_PPO_FLAGS_ALL) {
+        set_error("uavhip_ppo_step: flags 0x%x has bits outside UAVHIP_PPO_FLAGS_ALL (0x%x)", c->flags,
+                  UAVHIP_PPO_FLAGS_ALL);
+        return UAVHIP_EINVAL;
+    }
     hipStream_t st = (hipStream_t)stream;
     const Plan p = make_plan(c->minibatch, c->workspace);
     const int Bm = p.Bm, nblk = Bm / kHeadSamples;
@@ -671,11 +635,11 @@ extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const i
         io.fpart = p.fpart;
         io.vpart = p.vpart;
         io.eps_clip = c->eps_clip;
-        if (pos_split(Bm)) {  // K7: F1 / F2 / F3 (F3 writes the loss partials)
+        if (pos_split(c->flags, Bm)) {  // K7: F1 / F2 / F3 (F3 writes the loss partials)
             TR_CHECK(pol::policy_forward_ps(p.packed, states, io, Bm, st));
         } else {
-            io.split = split_blocks(Bm);
-            io.mix = fwd_mix();
+            io.split = split_blocks(c->flags, Bm);
+            io.mix = !(c->flags & UAVHIP_PPO_FIXED_ORDER_FWD);  // the trunk order mixed across workgroups
             TR_CHECK(pol::policy_forward_train(p.packed, states, io, Bm, st));
             if (io.split) TR_CHECK(pol::policy_loss_partials(io, Bm, st));
         }
@@ -710,7 +674,7 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
     const int ta = kActorTrunk, tc = kCriticTrunk;
     // partial rows: K6 one per 16-sample workgroup; K7 one per (block, position), row b * 5 + s, the
     // per-block layers (actor L0, critic L1: their pruned tails) at row b * 5
-    const bool ps = pos_split(Bm);
+    const bool ps = pos_split(c->flags, Bm);
     const int rstep = ps ? S : 1;                 // rows from one block's per-block partial row to the next
     const int full_parts = ps ? p.prows : nblk;    // critic L0 and the embeddings (K7: every row)
     {
@@ -732,7 +696,7 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         io.value_coef = c->value_coef;
         io.entropy_coef = c->entropy_coef;
         io.Bg = Bg;
-        io.gscale = grad_prescale(Bg);
+        io.gscale = grad_prescale(c->flags, Bg);
         io.vpart = p.vpart;
         io.nvpart = nblk;
         io.gsc_out = p.gsc;
@@ -741,8 +705,8 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         io.e[0] = p.e_a;
         io.e[1] = p.e_c;
         io.epart = p.epart;
-        io.split = ps ? 0 : split_blocks(Bm);
-        io.mix = bwd_mix();
+        io.split = ps ? 0 : split_blocks(c->flags, Bm);
+        io.mix = !(c->flags & UAVHIP_PPO_FIXED_ORDER_BWD);  // K6's trunk order mixed across workgroups
         const LayerBufs* lb[3] = {&A, &C0, &C1};
         for (int i = 0; i < 3; ++i)
             io.L[i] = pol::BwdLayerIO{lb[i]->qkv, lb[i]->xhat1, lb[i]->rstd1, lb[i]->u, lb[i]->xhat2, lb[i]->rstd2,
@@ -755,7 +719,6 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
     // ---------------------------------------------------------------- weight gradients
     SegBatch sb{};
     int seg_blocks = 0;
-    int sq_base = 0;  // direct-mode k_wgrad's g^2 partials come first in sq_part
     auto seg = [&](const float* src, int dst, int count, int parts, int part_stride, const float* src_rest = nullptr,
                    int dst_ld = 0) {
         if (sb.n >= kMaxSegs) { ++sb.n; return; }
@@ -796,15 +759,13 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         };
         // p3: the tiles that keep three-plane products (WgProb::p3_tiles): the key rows of in_proj,
         // whose sums cancel (softmax drops any per-query constant, so a sample's dk rows sum to
-        // zero); every other tile is two-plane. UAVHIP_WGRAD_PLANES=3: every tile three-plane.
-        const bool all3 = wgrad_all_three_planes();
+        // zero); every other tile is two-plane.
         auto dw = [&](const float* dY, int ldy, const XSrc& X, int ldx, int M, int N, int K, int dst_w, int p3 = 0) {
             dst[wp.b.n] = dst_w;
             wp.add(dY, ldy, X.x, ldx, M, N, K, X.mode, X.g, X.b);
             if (wp.ok) {
                 WgProb& Q = wp.b.p[wp.b.n - 1];
-                Q.dst = dst_w;
-                Q.p3_tiles = all3 ? ~0 : p3;
+                Q.p3_tiles = p3;
                 Q.rk = X.rk;
                 Q.rarg = X.rarg;
                 Q.rpb = K == R ? S * kHeadSamples : kHeadSamples;  // rows per 16-sample block
@@ -838,32 +799,18 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         dw(p.dz_c, HID, ln_out(C1.xhat2, tc, 1, N2W), D, HID, D, Bm, kOffs.o[kCriticHead]);
         wp.b.part = p.wg_part;
         wp.b.rt = p.rt;  // the forward's derived scales
-        if (wp.ok && wgrad_direct(wp.max_slabs())) {
-            // direct mode: one workgroup per output tile writes dW (unscaled) and its g^2 partial; the
-            // reduction below covers the other gradients, its g^2 partials after these
-            wp.b.direct = 1;
-            wp.b.grads = c->grads;
-            wp.b.sq = p.sq_part;
-            wp.b.unscale = 1.0f / grad_prescale(Bg);
-            wp.b.gsc = p.gsc;
-            wp.b.crit_off = kOffs.o[kCriticTrunk];
-            sq_base = wp.b.tiles;
-            hipLaunchKernelGGL(k_wgrad, dim3(wp.b.tiles), dim3(kWgThreads), 0, st, wp.b);
-            TR_CHECK(check_launch("k_wgrad"));
-        } else {
-            if (wp.ok && wgrad_chunked(wp.max_slabs()) && !wp.chunked(wgrad_p3_ratio())) wp.b.chunk = 0;
-            const bool sched = wp.ok && wp.tiles([&](const WgTileRuns& t) {
-                const WgProb& P = wp.b.p[t.prob];
-                seg(p.wg_part + (size_t)t.first_slot * kWgSlot, dst[t.prob] + t.m0 * P.N + t.n0, t.rows * kWgT, t.runs,
-                    t.run_stride * kWgSlot, p.wg_part + (size_t)t.rest_slot * kWgSlot, P.N);
-            });
-            if (!sched) {
-                set_error("uavhip_ppo_step: weight-gradient problems do not fit the stream-K schedule");
-                return UAVHIP_EINVAL;
-            }
-            hipLaunchKernelGGL(k_wgrad, dim3(wp.grid), dim3(kWgThreads), 0, st, wp.b);
-            TR_CHECK(check_launch("k_wgrad"));
+        if (wp.ok && wgrad_chunked(c->flags, wp.max_slabs()) && !wp.chunked()) wp.b.chunk = 0;
+        const bool sched = wp.ok && wp.tiles([&](const WgTileRuns& t) {
+            const WgProb& P = wp.b.p[t.prob];
+            seg(p.wg_part + (size_t)t.first_slot * kWgSlot, dst[t.prob] + t.m0 * P.N + t.n0, t.rows * kWgT, t.runs,
+                t.run_stride * kWgSlot, p.wg_part + (size_t)t.rest_slot * kWgSlot, P.N);
+        });
+        if (!sched) {
+            set_error("uavhip_ppo_step: weight-gradient problems do not fit the stream-K schedule");
+            return UAVHIP_EINVAL;
         }
+        hipLaunchKernelGGL(k_wgrad, dim3(wp.grid), dim3(kWgThreads), 0, st, wp.b);
+        TR_CHECK(check_launch("k_wgrad"));
     }
     // biases of the encoder layers (K6's per-workgroup sums of the dY rows)
     {
@@ -902,9 +849,9 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         return UAVHIP_EINVAL;
     }
     // padding floats between parameters stay zero
-    hipLaunchKernelGGL(k_reduce_grads, dim3(seg_blocks), dim3(256), 0, st, sb, c->grads, p.sq_part + sq_base, step,
-                       adam_hyper(c), p.adam_sc, 1.0f / grad_prescale(Bg), static_cast<const float*>(p.gsc),
+    hipLaunchKernelGGL(k_reduce_grads, dim3(seg_blocks), dim3(256), 0, st, sb, c->grads, p.sq_part, step,
+                       adam_hyper(c), p.adam_sc, 1.0f / grad_prescale(c->flags, Bg), static_cast<const float*>(p.gsc),
                        kOffs.o[kCriticTrunk], step ? p.packed + kRangeOff + kRgMax : nullptr);
-    *n_sq = sq_base + seg_blocks;
+    *n_sq = seg_blocks;
     return check_launch("k_reduce_grads");
 }

@@ -52,11 +52,9 @@ struct WgProb {
     int M, N, K, lda, ldb;
     int tiles_n, tiles, slabs;  // per problem: column tiles, tiles, slabs per tile
     int unit_begin;             // first slab unit of this problem
-    int tile_begin;             // first output tile of this problem (direct mode: its workgroup)
     int wg_begin;               // chunked mode: first workgroup (virtual index) of this problem
     int p3_tiles;               // bit t: tile t runs three-plane products (else two-plane)
     int chunk;                  // chunked mode: slabs per chunk of this problem's tiles
-    int dst;                    // direct mode: float offset of dW [M][N] in `grads`
     // the X operand's range (policy_layout.hpp): X is staged as X 2^-s and the run's dW multiplied by
     // 2^s (exact), s from a bound on |X| -- rk: kWgRStatic (rarg = the forward's static operand: its
     // (2^-s, 2^s) pair), kWgRE / kWgRA0 (layer 0's input / attention output of trunk rarg: from the
@@ -65,25 +63,15 @@ struct WgProb {
     const float* xmax;
 };
 enum { kWgRNone = 0, kWgRStatic = 1, kWgRE = 3, kWgRA0 = 4 };
-// Direct mode (small minibatches: every tile a few slabs): one workgroup per output tile runs all
-// of its slabs and writes dW itself -- times `unscale` (BwdIO::gscale undone, exact) -- into the
-// flat gradient, with the block's sum of squares in sq[blockIdx.x]; no partial tiles, no reduction.
 struct WgBatch {
     WgProb p[kWgMaxProbs];
     int n;
     int units;
     float* part;  // [grid * kWgRuns][kWgSlot]
-    int direct, tiles;
+    int tiles;       // output tiles of all problems
     int chunk, wgs;  // chunked mode: slabs per chunk (0: stream-K), workgroups holding work
-    float* grads;
-    float* sq;
-    float unscale;
-    const float* gsc;  // the critic's extra 2^k (heads_bwd): problems with dst >= crit_off
-    int crit_off;
     const float* rt;   // the training forward's derived scales (TrainIO::rtab_out, policy_layout.hpp kRtOp ..)
 };
-constexpr int kWgDirectMaxSlabs = 12;  // direct mode only when no tile has more slabs (K <= 384 rows)
-
 
 // Stamps (make TRACE=1 only): per workgroup, s_memtime at kernel start and, per run, after the
 // first slab landed / after the k-loop / after the epilogue (uavhip_wgrad_trace copies them out).
@@ -97,15 +85,6 @@ __device__ unsigned long long g_wtrace[kWgGrid * 16];
 #define WTR(slot) do {} while (0)
 #endif
 
-__device__ __forceinline__ int wg_find_tile(const WgBatch& b, int t) {
-    int lo = 0, hi = b.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (t >= b.p[mid].tile_begin) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 __device__ __forceinline__ int wg_find_wg(const WgBatch& b, int v) {
     int lo = 0, hi = b.n;
     while (hi - lo > 1) {
@@ -345,10 +324,6 @@ __global__ __launch_bounds__(kWgThreads) void k_wgrad(const WgBatch wb) {
         const int s0 = c * Q.chunk;
         u = Q.unit_begin + t * Q.slabs + s0;
         u_end = u + min(Q.chunk, Q.slabs - s0);
-    } else if (wb.direct) {  // workgroup = output tile: all of its slabs
-        const WgProb& Q = wb.p[wg_find_tile(wb, blockIdx.x)];
-        u = Q.unit_begin + (blockIdx.x - Q.tile_begin) * Q.slabs;
-        u_end = u + Q.slabs;
     }
     int run = 0;
     WTR(0);
@@ -369,35 +344,6 @@ __global__ __launch_bounds__(kWgThreads) void k_wgrad(const WgBatch wb) {
         else wg_kloop<false>(wg_smem, P, s0, n_slabs, m0, n0, mt0, nt0, hi, mid, lo, run, wb, wred, xinv);
         WTR(2 + 4 * run);
         // lane (i16, g) of tile (a, b) holds dW[m0 + 16 (mt0 + a) + 4 g + r][n0 + 16 (nt0 + b) + i16]
-        if (wb.direct) {  // the whole tile: dW itself, unscaled, rows < M (a 64-row problem), and g^2
-            float sq = 0.f;
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {
-                    const f32x4 v = (hi[a][b] + (mid[a][b] + lo[a][b] * (1.0f / 2048.0f)) * (1.0f / 2048.0f)) *
-                                    (P.dst >= wb.crit_off ? wb.unscale * wb.gsc[0] : wb.unscale) * xinv;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = m0 + 16 * (mt0 + a) + 4 * g + r;
-                        if (row < P.M) {
-                            wb.grads[P.dst + (size_t)row * P.N + n0 + 16 * (nt0 + b) + i16] = v[r];
-                            sq += v[r] * v[r];
-                        }
-                    }
-                }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) sq += __shfl_xor(sq, o);
-            float* red = reinterpret_cast<float*>(wg_smem);  // the stages are dead after the last barrier
-            if (l == 0) red[wv] = sq;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                float t = 0.f;
-                for (int w = 0; w < kWgThreads / 64; ++w) t += red[w];
-                wb.sq[blockIdx.x] = t;
-            }
-            return;
-        }
         float* out = wb.part + (size_t)(slot_wg * kWgRuns + run) * kWgSlot;
 #pragma unroll
         for (int a = 0; a < 4; ++a)
@@ -439,11 +385,9 @@ struct WgPlan {
         P.tiles = ((M + kWgT - 1) / kWgT) * P.tiles_n;
         P.slabs = K / kWgBK;
         P.unit_begin = b.units;
-        P.tile_begin = b.tiles;
         P.wg_begin = 0;
         P.p3_tiles = ~0;
         P.chunk = 0;
-        P.dst = 0;
         P.rk = kWgRNone;
         P.rarg = 0;
         P.rpb = 1;
@@ -457,14 +401,15 @@ struct WgPlan {
         return m;
     }
     // Chunked mode: the smallest chunk ch (slabs) whose (problem, chunk, tile) triples fit kWgGrid
-    // workgroups, where a problem with three-plane tiles gets chunks of ch * p3_ratio slabs (a
+    // workgroups, where a problem with three-plane tiles gets chunks of ch * kWgP3ChunkRatio slabs (a
     // three-plane slab costs more: 6 MFMAs and three planes against 4 and two, so its workgroups
-    // would otherwise finish last and set the launch's time); grid = the count rounded up to the 8
-    // XCDs. False if none fits.
-    bool chunked(float p3_ratio = 0.75f) {
+    // would otherwise finish last and set the launch's time; 0.75 is the measured per-slab cost
+    // ratio of the two forms); grid = the count rounded up to the 8 XCDs. False if none fits.
+    static constexpr float kWgP3ChunkRatio = 0.75f;
+    bool chunked() {
         const int ms = max_slabs();
         for (int ch = 1; ch <= ms; ++ch) {
-            const int ch3 = std::max(1, (int)(ch * p3_ratio + 0.5f));
+            const int ch3 = std::max(1, (int)(ch * kWgP3ChunkRatio + 0.5f));
             int wgs = 0;
             for (int i = 0; i < b.n; ++i) {
                 WgProb& P = b.p[i];

@@ -38,6 +38,9 @@ IST_COUNT = 12
 DST = dict(R=0, J=1, ASG_COST=2, COV_VALUE=3, TOTAL_COST=4, TOTAL_VALUE=5, PD_CUR=6, SUM_PDMG=7, SUM_PFIN=8)
 DST_COUNT = 12
 PPO_FORWARD, PPO_BACKWARD, PPO_UPDATE, PPO_FULL, PPO_PACKED = 1, 2, 4, 7, 8
+# uavhip_ppo.flags bits (0 = the measured defaults)
+PPO_NO_POS_SPLIT, PPO_NO_TRUNK_SPLIT, PPO_WGRAD_STREAM_K = 1, 2, 4
+PPO_FIXED_ORDER_FWD, PPO_FIXED_ORDER_BWD, PPO_NO_GRAD_PRESCALE = 8, 16, 32
 EP = dict(ENV=0, EPISODE=1, STEPS=2, REWARD=3, Q0=4, J_SUM=5, MAX_COV=6, ACTION1=7, VALID=8, PDMG_SUM=9,
           PFINAL_SUM=10, ASSIGN_STEPS=11)
 EP_COUNT = 12
@@ -73,7 +76,8 @@ class PPODesc(ctypes.Structure):
                 ("workspace", _vp), ("loss_sums", _vp), ("stats", _vp), ("n_floats", _i32), ("minibatch", _i32),
                 ("global_minibatch", _i32)] + \
               [(n, ctypes.c_double) for n in ("lr_actor", "lr_critic", "beta1", "beta2", "adam_eps")] + \
-              [(n, ctypes.c_float) for n in ("eps_clip", "max_grad_norm", "value_coef", "entropy_coef")]
+              [(n, ctypes.c_float) for n in ("eps_clip", "max_grad_norm", "value_coef", "entropy_coef")] + \
+              [("flags", _i32)]
 
 
 # name -> (restype, argtypes)
@@ -146,7 +150,7 @@ class UavHipError(RuntimeError):
     pass
 
 
-ABI_VERSION = 5  # include/uavhip.h uavhip_abi_version
+ABI_VERSION = 6  # include/uavhip.h uavhip_abi_version
 
 
 def _load():
@@ -155,9 +159,10 @@ def _load():
                           f"target-allocation-ppo-transformer_amd/csrc` (or __graft_entry__.build())")
     lib = ctypes.CDLL(LIB_PATH)
     # UAVHIP_ACCEPT_PREV_ABI=1 (set by the A/B timing scripts only, scripts/ab_rollout.py): an older
-    # experimental build may predate an entry point and be of the previous ABI (4: no range table,
-    # peers by ordinal). Anything else -- a custom UAVHIP_LIB included -- must be the current ABI with
-    # every entry point, so a stale build fails here, not later and far from the cause.
+    # experimental build may predate an entry point and be of the previous ABI (5: struct uavhip_ppo
+    # without `flags`, which such a build never reads). Anything else -- a custom UAVHIP_LIB included
+    # -- must be the current ABI with every entry point, so a stale build fails here, not later and far
+    # from the cause.
     lenient = os.environ.get("UAVHIP_ACCEPT_PREV_ABI") == "1"
     missing = [name for name in _SIGS if not hasattr(lib, name)]
     if missing and not lenient:

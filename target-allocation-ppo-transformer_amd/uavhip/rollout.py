@@ -15,17 +15,12 @@ step after T-1 is bootstrapped with V(s_T) (the reference only ever updates on c
 main_train.py:140-146, and uses next_value 0 at the buffer end). Pass bootstrap=False for the
 reference's rule.
 """
-import os
-
 import torch
 
 from . import _lib
 from .policy import rowproj_buffer
 from .ppo import gae, gae_workspace
 
-# UAVHIP_BOOTSTRAP_FULL=1: the bootstrap V(s_T) through the full forward (actor + sampling + critic)
-# instead of the critic-only launch -- the same values, bitwise (A/B switch of scripts/gpu_r04z.sh)
-_BOOTSTRAP_FULL = os.environ.get("UAVHIP_BOOTSTRAP_FULL", "0") == "1"
 # RolloutEngine(deferred_value=None): whether an engine built with default arguments takes the critic
 # off the step chain (DESIGN.md 10 has the measurements behind the setting)
 DEFERRED_VALUE_DEFAULT = True
@@ -181,7 +176,7 @@ class RolloutEngine:
                 ev[self.T][1].record()
             last = tr.last_values
         elif self.bootstrap:
-            if self.rowproj is not None and not _BOOTSTRAP_FULL:
+            if self.rowproj is not None:
                 # the critic alone (uavhip_policy_value_rows): nothing reads an action at step T; the
                 # actor ring row it skips is rebuilt by the next iteration's fill (step 0, fill=True)
                 ev = self.policy_events

@@ -38,11 +38,12 @@ from .policy import layout
 class FusedPPOTrainer:
     def __init__(self, policy, minibatch, lr_actor=None, lr_critic=None, eps_clip=None, max_grad_norm=None,
                  value_coef=0.5, entropy_coef=0.01, betas=(0.9, 0.999), adam_eps=1e-8, world=None, rank=None,
-                 group=None, allreduce=None, data_parallel=None):
+                 group=None, allreduce=None, data_parallel=None, flags=0):
         """minibatch: samples per optimizer step over all ranks (each rank runs minibatch / world).
         world / rank default to torch.distributed's (1 / 0 when not initialised); allreduce(t)
         sums a device tensor over the ranks in place (default: torch.distributed.all_reduce).
-        data_parallel: run the phase-split step with its two all-reduces (default: world > 1)."""
+        data_parallel: run the phase-split step with its two all-reduces (default: world > 1).
+        flags: uavhip_ppo.flags, _lib.PPO_* variant bits for comparisons and traces (0: the defaults)."""
         import torch.distributed as tdist
         ddp = tdist.is_available() and tdist.is_initialized()
         self.world = int(world if world is not None else (tdist.get_world_size(group) if ddp else 1))
@@ -89,6 +90,7 @@ class FusedPPOTrainer:
         d.eps_clip = cfg.EPS_CLIP if eps_clip is None else eps_clip
         d.max_grad_norm = cfg.GRAD_NORM_CLIP if max_grad_norm is None else max_grad_norm
         d.value_coef, d.entropy_coef = value_coef, entropy_coef
+        d.flags = int(flags)
         self.desc = d
         self.bufs = None
         self.graphs = {}    # steps per epoch -> captured epoch hipGraph over the current buffers

@@ -291,11 +291,12 @@ def test_update_repack_skip_matches_repacking_every_step(Bm):
 
 
 @pytest.mark.parametrize("Bm", [64, 1024])
-def test_trunk_split_matches_fused_trunks(Bm, monkeypatch):
+def test_trunk_split_matches_fused_trunks(Bm):
     """Minibatches of <= 2048 samples run the actor's and the critic's trunks in separate workgroups
     (train.hip split_blocks). Same arithmetic per trunk as the both-trunks workgroup: whole optimizer
     steps (forward, k_loss_partials, backward, weight gradients, Adam) give bitwise the same
-    parameters, loss statistics and Adam state as UAVHIP_TRUNK_SPLIT=0."""
+    parameters, loss statistics and Adam state as under UAVHIP_PPO_NO_TRUNK_SPLIT."""
+    from uavhip import _lib
     from uavhip.policy import TransformerActorCritic
     from uavhip.train import FusedPPOTrainer
     torch.manual_seed(8)
@@ -303,10 +304,9 @@ def test_trunk_split_matches_fused_trunks(Bm, monkeypatch):
     nets.append(copy.deepcopy(nets[0]))
     bufs = _buffers(3 * Bm, seed=14)
     out = []
-    monkeypatch.setenv("UAVHIP_POS_SPLIT", "0")  # minibatch 64 would otherwise run position-split (K7)
-    for net, flag in zip(nets, ("1", "0")):
-        monkeypatch.setenv("UAVHIP_TRUNK_SPLIT", flag)
-        tr = FusedPPOTrainer(net, Bm)
+    # minibatch 64 would otherwise run position-split (K7)
+    for net, flags in zip(nets, (_lib.PPO_NO_POS_SPLIT, _lib.PPO_NO_POS_SPLIT | _lib.PPO_NO_TRUNK_SPLIT)):
+        tr = FusedPPOTrainer(net, Bm, flags=flags)
         tr.set_buffers(*bufs)
         out.append((tr.run(epochs=2, generator=torch.Generator().manual_seed(3), use_graph=False), tr))
     (s1, t1), (s0, t0) = out
@@ -317,10 +317,10 @@ def test_trunk_split_matches_fused_trunks(Bm, monkeypatch):
 
 
 @pytest.mark.parametrize("Bm", [64, 256])
-def test_position_split_matches_fused_step(Bm, monkeypatch):
+def test_position_split_matches_fused_step(Bm):
     """Minibatches of <= 256 samples run position-split (K7, policy.hip: every full encoder layer as
     one workgroup per (16-sample block, window position), attention K / V and dK / dV through the
-    workspace). Against the 16-samples-per-workgroup kernels (UAVHIP_POS_SPLIT=0) on the same
+    workspace). Against the 16-samples-per-workgroup kernels (UAVHIP_PPO_NO_POS_SPLIT) on the same
     minibatch: loss sums to 1e-5 relative and every gradient tensor to 5e-5 of its max |grad| (the
     same bar as against torch autograd; the split sums the K / V gradient shares and the partial rows
     in another order), for a FULL step's FORWARD | BACKWARD."""
@@ -332,9 +332,8 @@ def test_position_split_matches_fused_step(Bm, monkeypatch):
     bufs = _buffers(3 * Bm, seed=42)
     idx = torch.randperm(3 * Bm, generator=torch.Generator().manual_seed(43))[:Bm].to(torch.int32).cuda()
     out = []
-    for flag in ("1", "0"):
-        monkeypatch.setenv("UAVHIP_POS_SPLIT", flag)
-        tr = FusedPPOTrainer(copy.deepcopy(base), Bm)
+    for flags in (0, _lib.PPO_NO_POS_SPLIT):
+        tr = FusedPPOTrainer(copy.deepcopy(base), Bm, flags=flags)
         tr.set_buffers(*bufs)
         tr.idx.copy_(idx)
         tr.step(_lib.PPO_FORWARD | _lib.PPO_BACKWARD)
@@ -445,50 +444,13 @@ def test_device_pack_matches_host_pack():
     _assert_packed_equal(packed, pack_weights(net.state_dict(), device="cuda"))
 
 
-def test_wgrad_direct_mode_matches_stream_k(monkeypatch):
-    """Minibatch 64: the weight-gradient GEMM in direct mode (one workgroup per output tile runs all
-    its slabs and writes dW and its g^2 partial itself; opt-in, UAVHIP_WGRAD_DIRECT=1: it measured
-    slower than stream-K at minibatch 64) against the default stream-K form with partial tiles summed
-    by k_reduce_grads (UAVHIP_WGRAD_DIRECT=0): the same products summed in another order, so every
-    gradient agrees to fp32 reordering (1e-6 of its tensor's max); and four whole optimizer steps
-    agree to the teacher-forced Adam bound's scale (parameters to 1e-6 lr-relative)."""
-    from uavhip import _lib
-    from uavhip.policy import TransformerActorCritic, layout
-    from uavhip.train import FusedPPOTrainer
-    torch.manual_seed(41)
-    base = TransformerActorCritic().cuda()
-    bufs = _buffers(256, seed=42)
-    idx = torch.randperm(256, generator=torch.Generator().manual_seed(43))[:64].to(torch.int32).cuda()
-    out = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("UAVHIP_WGRAD_DIRECT", mode)
-        tr = FusedPPOTrainer(copy.deepcopy(base), 64)
-        tr.set_buffers(*bufs)
-        g = tr.gradients(idx).clone()
-        for b in range(4):
-            tr.step(_lib.PPO_FULL | tr._packed(b), idx)
-        torch.cuda.synchronize()
-        out[mode] = (g, tr.params.clone(), tr.stats.clone())
-    offs, _ = layout()
-    for (k, p), o in zip(base.named_parameters(), offs):
-        a, b = out["0"][0][o:o + p.numel()], out["1"][0][o:o + p.numel()]
-        scale = float(a.abs().max())
-        err = float((a - b).abs().max())
-        assert err <= 1e-6 * scale + 1e-12, f"{k}: {err:.3e} vs max {scale:.3e}"
-    d = (out["0"][1] - out["1"][1]).abs()
-    print(f"4 steps, stream-K vs direct: max |d param| = {float(d.max()):.3e}, mean {float(d.mean()):.3e}")
-    # Adam normalises each element: an element with a near-zero gradient can turn fp32 reordering into
-    # a step difference of up to lr (tests/adam_bound.py); on average the runs agree closely
-    assert float(d.max()) <= 2 * 4 * 1e-3 and float(d.mean()) <= 1e-6
-    torch.testing.assert_close(out["0"][2], out["1"][2], rtol=1e-5, atol=1e-7)
-
-
-def test_wgrad_chunked_mode_matches_stream_k(monkeypatch):
+def test_wgrad_chunked_mode_matches_stream_k():
     """Minibatch 4096: the weight-gradient GEMM in chunked mode (the default for k ranges of >= 64
     slabs: one (chunk, tile) per workgroup, the tiles that share an operand slab consecutive on one
-    XCD, wgrad.hpp) against stream-K (UAVHIP_WGRAD_CHUNK=0): the same split products summed in
+    XCD, wgrad.hpp) against stream-K (UAVHIP_PPO_WGRAD_STREAM_K): the same split products summed in
     another grouping, so every gradient agrees to fp32 reordering (1e-5 of its tensor's max at 20480
     rows), the statistics to 1e-5, and both runs are deterministic (a repeat is bitwise equal)."""
+    from uavhip import _lib
     from uavhip.policy import TransformerActorCritic, layout
     from uavhip.train import FusedPPOTrainer
     torch.manual_seed(51)
@@ -496,9 +458,8 @@ def test_wgrad_chunked_mode_matches_stream_k(monkeypatch):
     bufs = _buffers(4096, seed=52)
     idx = torch.randperm(4096, generator=torch.Generator().manual_seed(53)).to(torch.int32).cuda()
     out = {}
-    for mode in ("0", "1"):
-        monkeypatch.setenv("UAVHIP_WGRAD_CHUNK", mode)
-        tr = FusedPPOTrainer(copy.deepcopy(base), 4096)
+    for mode, flags in (("0", _lib.PPO_WGRAD_STREAM_K), ("1", 0)):
+        tr = FusedPPOTrainer(copy.deepcopy(base), 4096, flags=flags)
         tr.set_buffers(*bufs)
         g = tr.gradients(idx).clone()
         g2 = tr.gradients(idx).clone()
@@ -516,13 +477,14 @@ def test_wgrad_chunked_mode_matches_stream_k(monkeypatch):
     print(f"chunked vs stream-K: worst |d| / tensor max = {worst:.3e}")
 
 
-def test_trunk_order_mix_is_bitwise(monkeypatch):
+def test_trunk_order_mix_is_bitwise():
     """Minibatch 4096 (no trunk split): the training forward with every other group of 8 workgroups
     running the critic trunk first (TrainIO::mix) and K6 with them running the actor first
-    (BwdIO::mix), both the default, against the fixed orders (UAVHIP_FWD_MIX=0, UAVHIP_BWD_MIX=0)
-    in all four combinations. Each workgroup computes the same values in another order of its two
-    independent trunks (K6's critic dz rows come back from the buffer heads_bwd wrote them to):
-    gradients and loss sums bitwise equal."""
+    (BwdIO::mix), both the default, against the fixed orders (UAVHIP_PPO_FIXED_ORDER_FWD,
+    UAVHIP_PPO_FIXED_ORDER_BWD) in all four combinations. Each workgroup computes the same values in
+    another order of its two independent trunks (K6's critic dz rows come back from the buffer
+    heads_bwd wrote them to): gradients and loss sums bitwise equal."""
+    from uavhip import _lib
     from uavhip.policy import TransformerActorCritic
     from uavhip.train import FusedPPOTrainer
     torch.manual_seed(61)
@@ -530,16 +492,52 @@ def test_trunk_order_mix_is_bitwise(monkeypatch):
     bufs = _buffers(4096, seed=62)
     idx = torch.randperm(4096, generator=torch.Generator().manual_seed(63)).to(torch.int32).cuda()
     out = {}
-    for mode in ("00", "01", "10", "11"):
-        monkeypatch.setenv("UAVHIP_FWD_MIX", mode[0])
-        monkeypatch.setenv("UAVHIP_BWD_MIX", mode[1])
-        tr = FusedPPOTrainer(copy.deepcopy(base), 4096)
+    for mode in ("00", "01", "10", "11"):  # forward, backward: 1 = mixed (the default), 0 = fixed order
+        flags = ((_lib.PPO_FIXED_ORDER_FWD if mode[0] == "0" else 0) |
+                 (_lib.PPO_FIXED_ORDER_BWD if mode[1] == "0" else 0))
+        tr = FusedPPOTrainer(copy.deepcopy(base), 4096, flags=flags)
         tr.set_buffers(*bufs)
         out[mode] = (tr.gradients(idx).clone(), tr.loss_sums.clone())
     torch.cuda.synchronize()
     for mode in ("01", "10", "11"):
         assert torch.equal(out["00"][0], out[mode][0]), mode
         assert torch.equal(out["00"][1], out[mode][1]), mode
+
+
+def test_environment_selects_no_kernel_path(monkeypatch):
+    """The update step's variants are chosen by uavhip_ppo.flags alone. Minibatch 64 is the smallest
+    legal one and the one where most of the retired environment switches used to bite (K7 against
+    K6, the trunk split, the direct weight-gradient mode). Two trainers with flags=0 on copies of one
+    network, the second built and run with all nine retired variables set to their former non-default
+    values: gradients, and after two optimizer steps the parameters, Adam state and loss statistics,
+    are bitwise equal."""
+    from uavhip import _lib
+    from uavhip.policy import TransformerActorCritic
+    from uavhip.train import FusedPPOTrainer
+    retired = {"UAVHIP_GRAD_PRESCALE": "0", "UAVHIP_POS_SPLIT": "0", "UAVHIP_TRUNK_SPLIT": "0",
+               "UAVHIP_WGRAD_DIRECT": "1", "UAVHIP_WGRAD_CHUNK": "1", "UAVHIP_WGRAD_PLANES": "3",
+               "UAVHIP_WGRAD_P3_RATIO": "0.5", "UAVHIP_FWD_MIX": "0", "UAVHIP_BWD_MIX": "0"}
+    torch.manual_seed(71)
+    base = TransformerActorCritic().cuda()
+    bufs = _buffers(128, seed=72)
+    idx = torch.randperm(128, generator=torch.Generator().manual_seed(73)).to(torch.int32).cuda()
+    out = []
+    for env in ({}, retired):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        tr = FusedPPOTrainer(copy.deepcopy(base), 64, flags=0)
+        tr.set_buffers(*bufs)
+        g = tr.gradients(idx[:64]).clone()
+        for b in range(2):
+            tr.step(_lib.PPO_FULL | tr._packed(b), idx[64 * b:64 * (b + 1)])
+        torch.cuda.synchronize()
+        out.append(dict(grads=g, params=tr.params.clone(), adam_m=tr.adam_m.clone(), adam_v=tr.adam_v.clone(),
+                        adam_step=tr.adam_step.clone(), loss_sums=tr.loss_sums.clone(), stats=tr.stats.clone()))
+    # two updates; three backward passes (the gradients() call and the two steps) in the loss statistics
+    assert float(out[0]["adam_step"]) == 2.0 and float(out[0]["stats"][3]) == 3.0
+    for k in out[0]:
+        d = int((out[0][k] != out[1][k]).sum())
+        assert d == 0, f"{k}: {d} elements differ with the retired variables set"
 
 
 def test_packed_weights_repack_on_device():
@@ -770,10 +768,11 @@ def test_gradients_per_element_vs_fp64(Bm, rscale, sscale):
     assert ph <= 2 * pt + 1e-6, (ph, pt)
 
 
-def test_gradient_prescale_ab(monkeypatch):
-    """A/B of the gradient pre-scale at Bm = 4096 (UAVHIP_GRAD_PRESCALE=0: the round-3 backward with
+def test_gradient_prescale_ab():
+    """A/B of the gradient pre-scale at Bm = 4096 (UAVHIP_PPO_NO_GRAD_PRESCALE: the round-3 backward with
     1/Bm folded into the per-sample loss gradient): the per-element error against fp64 autograd on
     the CPU, printed for both; the pre-scaled step must not be worse."""
+    from uavhip import _lib
     from uavhip.policy import TransformerActorCritic, layout
     from uavhip.train import FusedPPOTrainer
     Bm = 4096
@@ -784,9 +783,8 @@ def test_gradient_prescale_ab(monkeypatch):
     ref64, _ = _fp64_reference_grads(net, bufs, idx)
     offs, _ = layout()
     out = {}
-    for mode in ("1", "0"):
-        monkeypatch.setenv("UAVHIP_GRAD_PRESCALE", mode)
-        tr = FusedPPOTrainer(copy.deepcopy(net), Bm)
+    for mode, flags in (("1", 0), ("0", _lib.PPO_NO_GRAD_PRESCALE)):
+        tr = FusedPPOTrainer(copy.deepcopy(net), Bm, flags=flags)
         tr.set_buffers(*bufs)
         grads = tr.gradients(idx.cuda()).double().cpu()
         rels = []
@@ -796,6 +794,6 @@ def test_gradient_prescale_ab(monkeypatch):
             rels.append(((grads[o:o + p.numel()] - r).abs() / r.abs())[sel])
         rel = torch.cat(rels)
         out[mode] = (float(rel.quantile(0.5)), float(rel.quantile(0.99)), float(rel.max()))
-        print(f"UAVHIP_GRAD_PRESCALE={mode}: per-element rel error vs fp64 p50 {out[mode][0]:.2e} "
+        print(f"gradient pre-scale {'on' if mode == '1' else 'off'}: per-element rel error vs fp64 p50 {out[mode][0]:.2e} "
               f"p99 {out[mode][1]:.2e} max {out[mode][2]:.2e}")
     assert out["1"][1] <= out["0"][1] * 1.05

@@ -43,7 +43,7 @@ def test_library_exports_every_header_symbol():
     for f in fns:
         assert hasattr(_lib.LIB, f), f
     assert set(fns) == set(_lib.EXPORTS)
-    assert _lib.LIB.uavhip_abi_version() == _lib.ABI_VERSION == 5
+    assert _lib.LIB.uavhip_abi_version() == _lib.ABI_VERSION == 6
 
 
 def test_ctypes_mirrors_header_enums():
@@ -69,6 +69,12 @@ def test_ctypes_mirrors_header_enums():
     assert (ph["UAVHIP_PPO_FORWARD"], ph["UAVHIP_PPO_BACKWARD"], ph["UAVHIP_PPO_UPDATE"], ph["UAVHIP_PPO_FULL"],
             ph["UAVHIP_PPO_PACKED"]) == (_lib.PPO_FORWARD, _lib.PPO_BACKWARD, _lib.PPO_UPDATE, _lib.PPO_FULL,
                                          _lib.PPO_PACKED)
+    fl = _header_enum("uavhip_ppo_flag")
+    names = ("NO_POS_SPLIT", "NO_TRUNK_SPLIT", "WGRAD_STREAM_K", "FIXED_ORDER_FWD", "FIXED_ORDER_BWD",
+             "NO_GRAD_PRESCALE")
+    bits = [fl["UAVHIP_PPO_" + k] for k in names]
+    assert bits == [getattr(_lib, "PPO_" + k) for k in names] == [1 << i for i in range(6)]
+    assert fl["UAVHIP_PPO_FLAGS_ALL"] == sum(bits) and len(fl) == 7
 
 
 def _struct_fields(name):
@@ -122,6 +128,24 @@ def test_error_path_without_gpu():
     assert rc == -1 and b"bad env dims" in _lib.LIB.uavhip_last_error()
     with pytest.raises(_lib.UavHipError):
         _lib.check(rc, "uavhip_score_pairs")
+
+
+def test_ppo_step_rejects_undefined_flag_bits_without_gpu():
+    """uavhip_ppo.flags: a bit outside the UAVHIP_PPO_* variant bits is UAVHIP_EINVAL with a message
+    that names `flags`, before any HIP call. Every other field of the descriptor is valid (placeholder
+    pointers: validation never dereferences them), so the flags are what is refused."""
+    from uavhip import _lib
+    d = _lib.PPODesc()
+    for name in ("params", "grads", "adam_m", "adam_v", "adam_step", "workspace", "loss_sums", "stats"):
+        setattr(d, name, 16)
+    d.n_floats, d.minibatch, d.global_minibatch = _lib.LIB.uavhip_policy_layout(None, 0), 64, 64
+    d.lr_actor, d.lr_critic, d.beta1, d.beta2, d.adam_eps = 2e-4, 1e-3, 0.9, 0.999, 1e-8
+    d.eps_clip, d.max_grad_norm, d.value_coef, d.entropy_coef = 0.2, 1.0, 0.5, 0.01
+    args = (16, 16, 16, 16, 16, 16, 16, _lib.PPO_FULL, None)
+    for flags in (64, 63 | 1 << 20, -1):
+        d.flags = flags
+        assert _lib.LIB.uavhip_ppo_step(d, *args) == -1
+        assert b"uavhip_ppo_step: flags" in _lib.LIB.uavhip_last_error()
 
 
 def test_host_scene_generator_matches_reference(traj_npz):

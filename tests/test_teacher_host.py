@@ -79,7 +79,7 @@ def test_binding_signature():
     assert res is ctypes.c_int
     assert args == [ctypes.POINTER(_lib.EnvDesc), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     assert _lib.LIB.uavhip_teacher_steps.argtypes == args
-    assert _lib.ABI_VERSION == 5 and _lib.LIB.uavhip_abi_version() == 5
+    assert _lib.ABI_VERSION == 6 and _lib.LIB.uavhip_abi_version() == 6
 
 
 @pytest.mark.parametrize("N,M", SHAPES[:4] + [(3, 70)])
