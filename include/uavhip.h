@@ -451,6 +451,45 @@ int uavhip_refine_assignments(const uavhip_env* env, int32_t env_stride, int32_t
                               const int32_t* assignment_in, int32_t* assignment_out, double* J,
                               int32_t* covered, int32_t* stats, uavhip_stream_t stream);
 
+/* Exchange-move local search on J(X) (k_search, search.hip): uavhip_refine_assignments' best-response
+ * sweeps, which stop at the first allocation no single move improves, plus a second neighbourhood,
+ * the pairwise exchange: UAVs i and j swap their targets, one of which may be "none". Notation as
+ * above (list-order targets, P, v, c, w, a[u] in {-1, 0..M-1}); nothing contracted.
+ *   g(u, x, Q) = 0.0                                   if x == -1
+ *              = (v[x] * Q) * P[u][x] - (w * c[u])     otherwise
+ *   Qo(u)      = the product of (1.0 - P[k][a[u]]) over the UAVs k != u with a[k] == a[u],
+ *                ascending k, from 1.0   (1.0 when a[u] == -1)
+ *
+ *   a <- assignment_in converted exactly as uavhip_refine_assignments converts it; x <- 0
+ *   repeat:
+ *     PHASE: best-response sweeps from a, exactly uavhip_refine_assignments' sweep, until a sweep
+ *            makes no move or max_sweeps sweeps of this phase have run. sweeps, moves accumulate over
+ *            phases; phase_converged = 1 iff the phase ended on a sweep without a move, or
+ *            max_sweeps == 0.
+ *     if max_exchanges == 0: scan_clean = 0; stop                      (no scan is run)
+ *     SCAN:  for every pair i < j with a[i] != a[j]   (s = a[i], t = a[j]; at most one of them is -1):
+ *                d(i, j) = (g(j, s, Qo(i)) + g(i, t, Qo(j))) - (g(i, s, Qo(i)) + g(j, t, Qo(j)))
+ *            in that order of operations. j is not on s and i is not on t, so Qo(i) / Qo(j) are the
+ *            products over the other UAVs on s / t. The candidate is the pair with the largest d; of
+ *            equal d, the lowest i, then the lowest j.
+ *     if no pair has d > 0.0: scan_clean = 1; stop
+ *     if x == max_exchanges:  scan_clean = 0; stop
+ *     swap a[i], a[j]; x <- x + 1
+ * d(i, j) is the change of J under the swap in exact arithmetic. The loop runs at most
+ * max_exchanges + 1 phases, so it terminates whatever rounding does. J, covered and the id
+ * conversion of the result are uavhip_refine_assignments' own.
+ *  - env, env_stride, S, max_sweeps, assignment_in (nullable), assignment_out (required; may alias
+ *    assignment_in), J, covered (required): as uavhip_refine_assignments, with the same bounds;
+ *  - max_exchanges >= 0; with max_exchanges == 0 every output is bitwise
+ *    uavhip_refine_assignments', and stats[:, :4] is its stats;
+ *  - stats [S][6] int32 (nullable): sweeps run, moves made, phase_converged, invalid input ids,
+ *    exchanges made, scan_clean.
+ * The full N <= 64, M <= 128 range. The env's state and scene are only read; no allocation, no
+ * atomics, no grid-wide synchronisation. */
+int uavhip_search_assignments(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t max_exchanges,
+                              int32_t max_sweeps, const int32_t* assignment_in, int32_t* assignment_out,
+                              double* J, int32_t* covered, int32_t* stats, uavhip_stream_t stream);
+
 /* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
  * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
  * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is

@@ -1,0 +1,229 @@
+// refine_device.hpp -- the device side of the best-response local search on J(X), shared by k_refine
+// (refine.hip, uavhip_refine_assignments) and k_search (search.hip, uavhip_search_assignments): one
+// wave's view of one row -- the scene's registers, the id conversion, the sweeps and the scoring of
+// the result. Both translation units are built with -ffp-contract=off; the rule is in
+// include/uavhip.h.
+//
+// One wave per row. Lane t owns target t (and t + 64 when M > 64): its value, its id and the running
+// product Q; lane u owns a[u], p_pen[u] and omega c[u]. Q[t] is rebuilt for every UAV as the
+// ascending product over the other UAVs on t -- never kept incrementally, its rounding would depend
+// on the history of moves:
+//  * NCAP > 0 (M <= 64, N <= NCAP <= 32): lane t holds the column 1 - P[w][t], w < N, in registers
+//    and the rebuild is N readlanes of a[w] and a predicated multiply each: no memory access;
+//  * NCAP == 0 (N > 32 or M > 64): only the assigned UAVs contribute, so the rebuild loads the one
+//    element p_dmg[w][a[w]] per assigned w (L1 / L2 hits after the first sweep) in lane a[w].
+#pragma once
+#include "common.hpp"
+
+namespace uavhip {
+
+constexpr int kRefineWaves = 4;
+
+// maximum of (g, t) over the wave, the lowest t among equal g; every lane gets the result
+__device__ __forceinline__ void wave_argmax(double& g, int& t) {
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) {
+        const double go = __shfl_xor(g, m);
+        const int to = __shfl_xor(t, m);
+        if (go > g || (go == g && to < t)) {
+            g = go;
+            t = to;
+        }
+    }
+}
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int m = 1; m < kWave; m <<= 1) x = x + __shfl_xor(x, m);
+    return x;
+}
+
+template <int TPL, int NCAP>
+struct RefineRow {
+    static_assert(NCAP == 0 || TPL == 1, "the register column is the one-target-per-lane path");
+    int N, M, lane;
+    double omega;
+    const double* __restrict__ pd;  // p_dmg of the row's active scene, [N][M]
+    double v[TPL];                  // tgt_value of the lane's targets (0.0 beyond M)
+    int id[TPL];                    // tgt_id of the lane's targets
+    bool isu;
+    double pen, cost, wc;           // p_pen[lane], uav_cost[lane], omega * uav_cost[lane]
+    int a, invalid;                 // a[lane]: list index or -1; ids of the input that matched nothing
+    double om[NCAP > 0 ? NCAP : 1];
+    int sweeps, moves, converged;
+
+    // the scene of env s * stride (its active buffer) into registers; every UAV at -1
+    __device__ __forceinline__ void load(const uavhip_env& env, int s, int stride, int lane_) {
+        N = env.N;
+        M = env.M;
+        lane = lane_;
+        const long long e = (long long)s * stride;
+        const long long sb =
+            (env.scene_buffers == 2 ? (long long)(env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+        omega = env.prm[UAVHIP_PRM_OMEGA];
+        pd = env.p_dmg + sb * N * M;
+#pragma unroll
+        for (int j = 0; j < TPL; ++j) {
+            const int t = lane + kWave * j;
+            v[j] = t < M ? env.tgt_value[sb * M + t] : 0.0;
+            id[j] = t < M ? env.tgt_id[sb * M + t] : 0;
+        }
+        isu = lane < N;
+        pen = isu ? env.p_pen[sb * N + lane] : 0.0;
+        cost = isu ? env.uav_cost[sb * N + lane] : 0.0;
+        wc = omega * cost;
+        a = -1;
+        invalid = 0;
+        sweeps = 0;
+        moves = 0;
+        converged = 1;
+    }
+
+    // target ids -> list indices: a ballot against the lanes' ids, the lowest list index first
+    __device__ __forceinline__ void convert(const int* ain, int s) {
+        if (!ain) return;
+        const int idin = isu ? ain[(long long)s * N + lane] : -1;
+        for (int u = 0; u < N; ++u) {
+            const int want = readlane_i(idin, u);
+            if (want == -1) continue;
+            int idx = -1;
+#pragma unroll
+            for (int j = TPL - 1; j >= 0; --j) {
+                const unsigned long long m = ballot(lane + kWave * j < M && id[j] == want);
+                if (m) idx = kWave * j + ffs64(m);
+            }
+            if (idx < 0) ++invalid;
+            if (lane == u) a = idx;
+        }
+    }
+
+    __device__ __forceinline__ void load_columns() {
+        if constexpr (NCAP > 0) {
+#pragma unroll
+            for (int w = 0; w < NCAP; ++w) {
+                om[w] = 1.0;
+                if (w < N) {
+                    const double pw = readlane_d(pen, w);
+                    if (lane < M) om[w] = 1.0 - pd[w * M + lane] * pw;
+                }
+            }
+        }
+    }
+
+    // Q[j] = product of (1 - P[w][t]) over w != skip with a[w] == t, ascending w, from 1.0;
+    // cnt[j] = the number of those w
+    __device__ __forceinline__ void build_q(int skip, double (&Q)[TPL], int (&cnt)[TPL]) const {
+#pragma unroll
+        for (int j = 0; j < TPL; ++j) {
+            Q[j] = 1.0;
+            cnt[j] = 0;
+        }
+        if constexpr (NCAP > 0) {
+#pragma unroll
+            for (int w = 0; w < NCAP; ++w) {
+                if (w < N) {
+                    const int aw = readlane_i(a, w);
+                    if (aw == lane && w != skip) {
+                        Q[0] = Q[0] * om[w];
+                        ++cnt[0];
+                    }
+                }
+            }
+        } else {
+            for (int w = 0; w < N; ++w) {
+                const int aw = readlane_i(a, w);
+                if (aw < 0 || w == skip) continue;
+                const double pw = readlane_d(pen, w);
+#pragma unroll
+                for (int j = 0; j < TPL; ++j) {
+                    if (aw == lane + kWave * j) {
+                        Q[j] = Q[j] * (1.0 - pd[w * M + aw] * pw);
+                        ++cnt[j];
+                    }
+                }
+            }
+        }
+    }
+
+    // best-response sweeps from a, until a sweep makes no move or max_sweeps sweeps of this call
+    // have run; sweeps and moves accumulate over calls, converged is this call's
+    __device__ __forceinline__ void phase(int max_sweeps) {
+        const long long last = (long long)sweeps + max_sweeps;
+        converged = 1;
+        while (sweeps < last) {
+            int moved = 0;
+            for (int u = 0; u < N; ++u) {
+                double Q[TPL];
+                int cnt[TPL];
+                build_q(u, Q, cnt);
+                const double pu = readlane_d(pen, u), wcu = readlane_d(wc, u);
+                double g[TPL];
+                double bg = -__builtin_huge_val();
+                int bt = 0x7fffffff;
+#pragma unroll
+                for (int j = 0; j < TPL; ++j) {
+                    const int t = lane + kWave * j;
+                    g[j] = -__builtin_huge_val();
+                    if (t < M) {
+                        const double p = pd[u * M + t] * pu;
+                        g[j] = (v[j] * Q[j]) * p - wcu;
+                        if (g[j] > bg) {
+                            bg = g[j];
+                            bt = t;
+                        }
+                    }
+                }
+                wave_argmax(bg, bt);
+                bg = readlane_d(bg, 0);
+                bt = readlane_i(bt, 0);
+                const int au = readlane_i(a, u);
+                double cur = 0.0;
+                if (au >= 0) {
+                    if constexpr (TPL == 2)
+                        cur = readlane_d(au >= kWave ? g[1] : g[0], au & (kWave - 1));
+                    else
+                        cur = readlane_d(g[0], au);
+                }
+                const bool some = bg > 0.0;
+                const int cand = some ? bt : -1;
+                const double cg = some ? bg : 0.0;
+                if (cg > cur) {
+                    if (lane == u) a = cand;
+                    ++moves;
+                    moved = 1;
+                }
+            }
+            ++sweeps;
+            converged = !moved;
+            if (!moved) break;
+        }
+    }
+
+    // J and covered of a, and a as target ids
+    __device__ __forceinline__ void finish(int s, int* aout, double* __restrict__ J, int* __restrict__ covered) const {
+        double Q[TPL];
+        int cnt[TPL];
+        build_q(-1, Q, cnt);
+        double val = 0.0;
+        int cov = 0;
+#pragma unroll
+        for (int j = 0; j < TPL; ++j) {
+            val = val + v[j] * (1.0 - Q[j]);  // v = 0 beyond M
+            cov += __popcll(ballot(cnt[j] > 0));
+        }
+        val = wave_sum(val);
+        const double csum = wave_sum(a >= 0 ? cost : 0.0);
+        const int src = a < 0 ? 0 : a;
+        int out = __shfl(id[0], src & (kWave - 1));
+        if constexpr (TPL == 2) {
+            const int hi = __shfl(id[1], src & (kWave - 1));
+            out = src >= kWave ? hi : out;
+        }
+        if (isu) aout[(long long)s * N + lane] = a < 0 ? -1 : out;
+        if (lane == 0) {
+            J[s] = val - omega * csum;
+            covered[s] = cov;
+        }
+    }
+};
+
+}  // namespace uavhip

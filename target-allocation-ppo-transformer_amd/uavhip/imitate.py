@@ -22,6 +22,10 @@ epochs move the policy, rows whose ratio has left [1 - eps, 1 + eps] upwards sto
 clip is a trust region per batch. old_values = the current values, so the clipped value loss is the
 plain (v - R)^2 at the first step, R the discounted return-to-go of the teacher's episode.
 
+ImitationRun(teacher_exchanges=X) / --teacher-exchanges X (source "teacher" only; 0, the default, is the
+path above) takes the teacher allocation from VecUAVEnv.search_assignments(None, max_exchanges=X)
+instead: the same search with pairwise exchanges between the sweeps.
+
 Seeding contract (tests/test_gpu_imitate.py relies on it): torch.manual_seed(seed) before
 TransformerActorCritic(); iteration i = 1, 2, .. draws its scenes with env.desc.seed = seed + i (as
 AllocationSolver._generate_scenes sets it) after zeroing istate; minibatch orders from
@@ -78,15 +82,18 @@ class TeacherBatch:
 
 
 @torch.no_grad()
-def teacher_batch(env, assignment=None, max_sweeps=32, gamma=None):
+def teacher_batch(env, assignment=None, max_sweeps=32, gamma=None, exchanges=0):
     """Reset `env`, walk it along `assignment` ([E, N] int32 target ids or -1; None: the baseline,
-    env.refine_assignments(None, max_sweeps=max_sweeps)) in one uavhip_teacher_steps launch of N * M
-    steps, and return the episodes as a TeacherBatch. returns = uavhip.ppo.gae with zero values and
-    lambda = 1: ret_t = r_t + gamma (1 - done_t) ret_{t+1}."""
+    env.refine_assignments(None, max_sweeps=max_sweeps), or with exchanges = X > 0 the search with
+    pairwise exchanges, env.search_assignments(None, max_exchanges=X, max_sweeps=max_sweeps)) in one
+    uavhip_teacher_steps launch of N * M steps, and return the episodes as a TeacherBatch. returns =
+    uavhip.ppo.gae with zero values and lambda = 1: ret_t = r_t + gamma (1 - done_t) ret_{t+1}."""
     from . import _lib
     from .ppo import gae
     env.reset()
-    if assignment is None:
+    if assignment is None and exchanges > 0:
+        assignment, teacher_J, _, _ = env.search_assignments(None, max_exchanges=exchanges, max_sweeps=max_sweeps)
+    elif assignment is None:
         assignment, teacher_J, _, _ = env.refine_assignments(None, max_sweeps=max_sweeps)
     else:
         _, teacher_J, _, _ = env.refine_assignments(assignment, max_sweeps=0)
@@ -218,7 +225,8 @@ def imitation_update(trainer, policy, batch, epochs, generator, assign_weight=1.
             "assign_agreement": q[4], "optimizer_steps": int(cnt)}
 
 
-def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0, source="teacher", expert_share=0.25):
+def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0, source="teacher", expert_share=0.25,
+                  teacher_exchanges=0):
     """ImitationRun's argument checks that need no device; each message names the argument."""
     if minibatch <= 0 or minibatch % 64:
         raise ValueError(f"minibatch={minibatch}: must be a positive multiple of 64 (the training step's tile)")
@@ -240,23 +248,31 @@ def validate_args(envs, uavs, targets, minibatch, epochs, eval_every=0, source="
                          f"(uavs={uavs}, targets={targets}); source='expert' has no such limit")
     if not 0.0 <= expert_share <= 1.0:
         raise ValueError(f"expert_share={expert_share}: must be in [0, 1]")
+    if teacher_exchanges < 0:
+        raise ValueError(f"teacher_exchanges={teacher_exchanges}: must be >= 0 (0 = the plain best-response teacher)")
+    if teacher_exchanges > 0 and source != "teacher":
+        raise ValueError(f"teacher_exchanges={teacher_exchanges}: source='teacher' only (source={source!r} takes its "
+                         f"labels from the state-wise expert)")
 
 
 class ImitationRun:
     def __init__(self, envs, uavs, targets, minibatch, out_dir, seed=0, epochs=None, eval_every=0, eval_scenes=1024,
                  eval_seed=1, max_sweeps=32, assign_weight=1.0, lr_actor=None, lr_critic=None, eps_clip=None,
                  max_grad_norm=None, value_coef=0.5, entropy_coef=0.01, device="cuda:0", source="teacher",
-                 expert_share=0.25):
+                 expert_share=0.25, teacher_exchanges=0):
         """source: "teacher" (the baseline's episodes), "expert" (the state-wise expert's own walk) or
         "dagger" (the learner's sampled walk, relabelled by the expert; module docstring).
-        expert_share: under "dagger", the share of envs that follow the expert instead."""
+        expert_share: under "dagger", the share of envs that follow the expert instead.
+        teacher_exchanges: under "teacher", X > 0 takes the teacher allocation from the search with at
+        most X pairwise exchanges (uavhip_search_assignments) instead of the plain refinement."""
         self.E, self.N, self.M = int(envs), int(uavs), int(targets)
         self.minibatch = int(minibatch)
         self.epochs = int(cfg.K_EPOCHS if epochs is None else epochs)
         self.eval_every = int(eval_every)
         self.source, self.expert_share = source, float(expert_share)
+        self.teacher_exchanges = int(teacher_exchanges)
         validate_args(self.E, self.N, self.M, self.minibatch, self.epochs, self.eval_every, self.source,
-                      self.expert_share)
+                      self.expert_share, self.teacher_exchanges)
         self.eval_scenes, self.eval_seed = int(eval_scenes), int(eval_seed)
         self.max_sweeps, self.assign_weight = int(max_sweeps), float(assign_weight)
         self.seed = int(seed)
@@ -328,7 +344,7 @@ class ImitationRun:
         env.istate.zero_()
         env.generate_scenes()
         if self.source == "teacher":
-            batch = teacher_batch(env, None, max_sweeps=self.max_sweeps)
+            batch = teacher_batch(env, None, max_sweeps=self.max_sweeps, exchanges=self.teacher_exchanges)
         else:
             self.batch = None  # run.batch is the last ExpertBatch; released before the next is made
             learner = self.source == "dagger" and it >= 2
@@ -388,11 +404,14 @@ def main(argv=None):
                          "learner's sampled walk relabelled by the expert")
     ap.add_argument("--expert-share", type=float, default=0.25,
                     help="dagger: the share of envs that follow the expert instead of the learner's trace")
+    ap.add_argument("--teacher-exchanges", type=int, default=0, metavar="X",
+                    help="teacher: the teacher allocation from the search with at most X pairwise exchanges "
+                         "(0: the plain best-response search)")
     a = ap.parse_args(argv)
     run = ImitationRun(a.envs, a.uavs, a.targets, a.minibatch, a.out, seed=a.seed, epochs=a.epochs,
                        eval_every=a.eval_every, eval_scenes=a.eval_scenes, eval_seed=a.eval_seed,
                        max_sweeps=a.max_sweeps, assign_weight=a.assign_weight, source=a.source,
-                       expert_share=a.expert_share)
+                       expert_share=a.expert_share, teacher_exchanges=a.teacher_exchanges)
     print(json.dumps(run.fit(a.iterations)))
 
 

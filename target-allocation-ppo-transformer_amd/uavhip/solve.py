@@ -14,17 +14,21 @@ learned constructive solver is used).
 
     alloc = solver.solve(num_scenes=4096, seed=0, refine=32)   # + best-response local search on J
     base = solver.baseline(num_scenes=4096, seed=0)            # the same scenes without the policy
+    alloc = solver.solve(num_scenes=4096, seed=0, refine=32, exchanges=32)   # + pairwise exchanges
 
 The env accepts or rejects an assignment on r(X), in one pass of the pointer walk; refine = R > 0
 polishes the chosen replica's allocation on J(X) itself (uavhip_refine_assignments: every UAV in turn
 moves to the target, or to none, where its marginal contribution to J is largest, at most R sweeps),
 and baseline() runs that search from the empty assignment -- the non-learned yardstick a
-checkpoint's mean J is read against.
+checkpoint's mean J is read against. exchanges = X > 0 (solve and baseline) runs the search with a second
+neighbourhood instead (uavhip_search_assignments): where no single move improves J, the best swap of
+two UAVs' targets is made and the sweeps run again, at most X times.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-[--refine SWEEPS] [--baseline] prints one JSON line (mean / best J, mean covered, mean steps,
+[--refine SWEEPS] [--exchanges X] [--baseline] prints one JSON line (mean / best J, mean covered, mean steps,
 scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
-scenes where the policy beats the baseline).
+scenes where the policy beats the baseline; with --exchanges also mean_exchanges and, beside the plain
+mean_J_baseline, mean_J_baseline_exchange).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
@@ -52,7 +56,8 @@ class Allocation:
     replica_J: torch.Tensor     # [S, K] f64: J of every replica as decoding left it
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
     decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
-    refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids
+    refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
+    #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean
 
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
@@ -149,7 +154,7 @@ class AllocationSolver:
         return env
 
     @torch.no_grad()
-    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0):
+    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0):
         """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
         `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
         greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
@@ -158,10 +163,17 @@ class AllocationSolver:
         best-response local search on J (uavhip_refine_assignments); assignment / J / covered are
         then the refined ones, decoded_J the J before and refine_stats the search's counters. A
         scene where no replica finished (best_replica == -1) is refined from the empty assignment.
-        refine = 0 launches nothing more and changes nothing."""
-        refine = int(refine)
+        refine = 0 launches nothing more and changes nothing.
+        exchanges = X > 0 (needs refine > 0): the polish is uavhip_search_assignments with at most X
+        pairwise exchanges and R sweeps per phase, refine_stats its [S, 6] counters. exchanges = 0 is
+        the plain refinement: the same launches, the same results."""
+        refine, exchanges = int(refine), int(exchanges)
         if refine < 0:
             raise ValueError("solve: refine must be >= 0")
+        if exchanges < 0:
+            raise ValueError("solve: exchanges must be >= 0")
+        if exchanges > 0 and refine == 0:
+            raise ValueError("solve: exchanges > 0 needs refine > 0 (the sweeps between the exchanges)")
         scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
         with torch.cuda.device(self.device):
@@ -180,20 +192,32 @@ class AllocationSolver:
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
             if refine == 0:
                 return Allocation(assignment, J, covered, best, steps, replica_J, actions)
-            refined, rJ, rcov, stats = env.refine_assignments(assignment, stride=K, rows=S, max_sweeps=refine)
+            if exchanges > 0:
+                refined, rJ, rcov, stats = env.search_assignments(assignment, stride=K, rows=S, max_exchanges=exchanges,
+                                                                  max_sweeps=refine)
+            else:
+                refined, rJ, rcov, stats = env.refine_assignments(assignment, stride=K, rows=S, max_sweeps=refine)
         return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats)
 
     @torch.no_grad()
-    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32):
+    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0):
         """The non-learned yardstick for the same objective: the scenes solve() would run (scene for
         scene under the same `seed`), no policy launch, the best-response local search started from
         the empty assignment (a greedy constructor plus local search). Returns an Allocation whose
-        decode-only fields (best_replica, steps, replica_J) are zeros."""
+        decode-only fields (best_replica, steps, replica_J) are zeros. exchanges = X > 0: the search
+        with at most X pairwise exchanges (uavhip_search_assignments), refine_stats [S, 6]."""
+        exchanges = int(exchanges)
+        if exchanges < 0:
+            raise ValueError("baseline: exchanges must be >= 0")
         scenes, S, seed = self._scene_args("baseline", scenes, num_scenes, seed)
         K = self.K
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
-            assignment, J, covered, stats = env.refine_assignments(None, stride=K, rows=S, max_sweeps=max_sweeps)
+            if exchanges > 0:
+                assignment, J, covered, stats = env.search_assignments(None, stride=K, rows=S, max_exchanges=exchanges,
+                                                                       max_sweeps=max_sweeps)
+            else:
+                assignment, J, covered, stats = env.refine_assignments(None, stride=K, rows=S, max_sweeps=max_sweeps)
             zi = torch.zeros(S, dtype=torch.int32, device=env.device)
             zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
         return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
@@ -215,20 +239,26 @@ def main(argv=None):
     ap.add_argument("--targets", type=int, default=default_cfg.NUM_TARGETS)
     ap.add_argument("--refine", type=int, default=0, metavar="SWEEPS",
                     help="polish each allocation by at most SWEEPS sweeps of the best-response local search on J")
+    ap.add_argument("--exchanges", type=int, default=0, metavar="X",
+                    help="with --refine: at most X pairwise exchanges between the sweeps (uavhip_search_assignments); "
+                         "with --baseline: also the baseline with exchanges, beside the plain one")
     ap.add_argument("--baseline", action="store_true",
                     help="also run the non-learned baseline (the local search from the empty assignment) on the "
                          "same scenes and report the share of scenes where the policy's J is larger")
     a = ap.parse_args(argv)
+    if a.exchanges < 0:
+        ap.error("--exchanges must be >= 0")
     if not torch.cuda.is_available():
         raise RuntimeError("uavhip.solve decodes on the GPU (HIP) only")
     dev = torch.device("cuda:0")
     policy = TransformerActorCritic().to(dev)
     load_checkpoint(policy, a.checkpoint)
     solver = AllocationSolver(policy, a.uavs, a.targets, samples=a.samples)
-    solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine)  # warm-up: allocation, weight pack
+    ex = a.exchanges if a.refine > 0 else 0  # without --refine, --exchanges is the baseline's alone
+    solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine, exchanges=ex)  # warm-up: allocation, weight pack
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine)
+    r = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine, exchanges=ex)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     r = r.cpu()
@@ -238,9 +268,14 @@ def main(argv=None):
            "unfinished": int((r.best_replica < 0).sum()), "scenes_per_s": a.scenes / dt}
     if a.refine > 0:
         out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
+        if a.exchanges > 0:
+            out.update(mean_exchanges=float(r.refine_stats[:, 4].double().mean()))
     if a.baseline:
         b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
         out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
+        if a.exchanges > 0:
+            bx = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges).cpu()
+            out.update(mean_J_baseline_exchange=float(bx.J.mean()))
     print(json.dumps(out))
 
 

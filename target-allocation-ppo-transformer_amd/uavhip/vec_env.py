@@ -278,6 +278,40 @@ class VecUAVEnv:
                                             ptr(covered), ptr(stats), stream_handle()), "uavhip_refine_assignments")
         return out, J, covered, stats
 
+    def search_assignments(self, assignment=None, stride=1, rows=None, max_exchanges=32, max_sweeps=32, out=None,
+                           J=None, covered=None, stats=None):
+        """uavhip_search_assignments: refine_assignments' best-response search plus the pairwise
+        exchange -- where no single move improves J, the best swap of two UAVs' targets (one may be
+        "none") is made and the sweeps run again, at most max_exchanges times, max_sweeps sweeps per
+        phase. Arguments as refine_assignments. Returns (assignment [rows, N] int32 target ids,
+        J [rows] f64, covered [rows] int32, stats [rows, 6] int32: sweeps, moves, the last phase
+        converged, invalid input ids, exchanges made, 1 if the last scan found no improving pair).
+        max_exchanges = 0 is refine_assignments, bitwise. The env is only read."""
+        stride, max_exchanges, max_sweeps = int(stride), int(max_exchanges), int(max_sweeps)
+        if stride < 1:
+            raise ValueError(f"search_assignments: stride={stride} must be >= 1")
+        S = (self.E - 1) // stride + 1 if rows is None else int(rows)
+        if S < 1 or (S - 1) * stride >= self.E:
+            raise ValueError(f"search_assignments: rows={S} at stride={stride} do not fit E={self.E}")
+        if max_exchanges < 0:
+            raise ValueError(f"search_assignments: max_exchanges={max_exchanges} must be >= 0")
+        if max_sweeps < 0:
+            raise ValueError(f"search_assignments: max_sweeps={max_sweeps} must be >= 0")
+        dev = self.device
+        out = torch.empty(S, self.N, dtype=torch.int32, device=dev) if out is None else out
+        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
+        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
+        stats = torch.empty(S, 6, dtype=torch.int32, device=dev) if stats is None else stats
+        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
+        check_out(out, "out", torch.int32, (S, self.N), dev)
+        check_out(J, "J", torch.float64, (S,), dev)
+        check_out(covered, "covered", torch.int32, (S,), dev)
+        check_out(stats, "stats", torch.int32, (S, 6), dev)
+        check(LIB.uavhip_search_assignments(self.desc, stride, S, max_exchanges, max_sweeps, ptr(assignment), ptr(out),
+                                            ptr(J), ptr(covered), ptr(stats), stream_handle()),
+              "uavhip_search_assignments")
+        return out, J, covered, stats
+
     def teacher_steps(self, assignment, n_max=None, obs=None, actions=None, reward=None, done=None, info=None,
                       steps=None, finished=None, ep_return=None, stats=None, want_info=False):
         """uavhip_teacher_steps: walk every env from its current state (reset it first) along
