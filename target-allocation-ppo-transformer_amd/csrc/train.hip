@@ -245,11 +245,20 @@ constexpr int kSqBlocks = 256;
 // make_golden.py, no GPU). On a CUDA device (agents/ppo.py:14 when one is present) torch defaults to
 // the foreach path, p + step * (m / denom): one rounding apart per element, inside the teacher-forced
 // bound of tests/adam_bound.py; parity with that path is bounded, not bitwise:
+//   g = g * coef,  coef = min(max_norm / (norm + 1e-6f), 1)    (torch: reciprocal * max_norm, the same
+//                                                                value for a power-of-two max_norm)
 //   m = lerp(m, g, 1 - b1)            = fma(w1, g - m, m)       (the vectorised lerp, weight < 0.5)
-//   v = v * b2;  v = addcmul(v, g, g, 1 - b2) = v + ((1 - b2) g) g
+//   v = v * b2;  v = addcmul(v, g, g, 1 - b2) = fma(w2 g, g, v b2)
 //   denom = sqrt(v) / sqrt(1 - b2^t) + eps
 //   p = addcdiv(p, m, denom, -lr / (1 - b1^t)) = p + ((-step) m) / denom
-// with the step-dependent scalars from AdamScalars; no other contraction (explicit _rn operations).
+// with the step-dependent scalars from AdamScalars. Exactly two operations are fused, because torch's
+// CPU kernels are (measured bitwise on torch 2.10, tests/test_adam_model_host.py): the lerp's
+// w1 * (g - m) + m, and in v the product (w2 g) * g with the sum after it. w2 * g and v * b2 are each
+// rounded on their own, as are g - m, the square root, both divisions, + eps, nss * m and the final
+// sum (contraction is off for the block; the two fusions are explicit __fmaf_rn). One difference
+// from torch remains: the square root here is correctly rounded, torch's CPU sqrt (MKL) is one ulp low
+// for about 0.5 % of inputs, which reaches p in a few elements per 100 000. tests/adam_model.py restates
+// this arithmetic in numpy; tests/test_gpu_adam_update.py holds the kernel to it bit for bit.
 //
 // Work items: one float4 per thread, 256 per block; each parameter's items start a new block, so
 // a block's parameter is a table lookup. A GEMM weight's block (kTileK != 0, flat [NR][NC]) covers
@@ -357,8 +366,10 @@ __global__ __launch_bounds__(256) void k_adam(const AdamArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             m[j] = __fmaf_rn(w1, g[j] - m[j], m[j]);  // torch's vectorised lerp: one fma
-            v[j] = v[j] * b2 + (w2 * g[j]) * g[j];
-            const float denom = __fdiv_rn(__fsqrt_rn(v[j]), sc.bc2s) + epsf;
+            v[j] = __fmaf_rn(w2 * g[j], g[j], v[j] * b2);  // torch's mul_ + addcmul_: the last product fused
+            // sqrtf, not __fsqrt_rn: in this toolchain the intrinsic is the native v_sqrt_f32 (1 ulp),
+            // sqrtf the correctly rounded sequence (hipcc's default for fp32 divide and sqrt)
+            const float denom = __fdiv_rn(sqrtf(v[j]), sc.bc2s) + epsf;
             p[j] = p[j] + __fdiv_rn(nss * m[j], denom);
         }
         *reinterpret_cast<f32x4*>(a.grads + f) = g;
