@@ -637,6 +637,32 @@ int uavhip_ppo_step(const uavhip_ppo* ppo, const float* states, const int8_t* ac
                     const float* old_values, const float* returns, const float* advantages, const int32_t* idx,
                     int32_t phases, uavhip_stream_t stream);
 
+/* The four hyper-parameters a schedule changes during a run, as a device buffer hyper[UAVHIP_HP_COUNT]
+ * of doubles: values in device memory can change between replays of a captured graph that holds the
+ * step, by-value kernel arguments cannot. */
+enum uavhip_ppo_hyper {
+    UAVHIP_HP_LR_ACTOR = 0,   /* read as a double where Adam's step scalars are formed (once per UPDATE,
+                                 by the block that advances adam_step), as ppo->lr_actor is            */
+    UAVHIP_HP_LR_CRITIC,      /* likewise, for ppo->lr_critic                                          */
+    UAVHIP_HP_ENTROPY_COEF,   /* used as (float)hyper[i] (one double -> float rounding) by BACKWARD     */
+    UAVHIP_HP_EPS_CLIP,       /* used as (float)hyper[i] by FORWARD (the loss sums) and BACKWARD        */
+    UAVHIP_HP_COUNT
+};
+
+/* uavhip_ppo_step with the four values of uavhip_ppo_hyper read from `hyper` (device memory) by the
+ * kernels when they RUN, not when they are launched or captured. hyper == NULL: exactly
+ * uavhip_ppo_step (which is this call with NULL). hyper != NULL: ppo->lr_actor, lr_critic,
+ * entropy_coef and eps_clip are ignored, in every phase (pass the same buffer to the FORWARD,
+ * BACKWARD and UPDATE calls of a phase-split step); value_coef, max_grad_norm, the betas and
+ * adam_eps stay by value. A buffer holding the descriptor's own values (the floats widened to
+ * double) gives bitwise the by-value step; no launch is added in either mode. The buffer must stay
+ * valid and unchanged while a step, or a captured graph holding one, is in flight: write it
+ * stream-ordered between steps / replays. The values are not validated on the device (the caller
+ * does: finite, learning rates and entropy_coef >= 0, eps_clip > 0; uavhip/train.py set_hyper). */
+int uavhip_ppo_step_hyper(const uavhip_ppo* ppo, const double* hyper, const float* states, const int8_t* actions,
+                          const float* old_logp, const float* old_values, const float* returns,
+                          const float* advantages, const int32_t* idx, int32_t phases, uavhip_stream_t stream);
+
 /* Update diagnostics of a batch of n samples (csrc/ppo_diag.hip), out[UAVHIP_DIAG_COUNT] f64. With
  * d_i = (double)new_logp_i - (double)old_logp_i and r_i = exp(d_i), all arithmetic in double: */
 enum uavhip_diag {

@@ -44,8 +44,9 @@ __global__ __launch_bounds__(64) void k_loss_partials(const TrainIO io) {
     const int b0 = blockIdx.x * SPW;
     if (TIDX() < SPW) {
         const float* o = io.smp + (size_t)(b0 + TIDX()) * 8;
+        const float eps_clip = hyper_f32(io.hyper, UAVHIP_HP_EPS_CLIP, io.eps_clip);
         const float oi[5] = {o[0], o[1], o[2], o[3], o[4]};
-        loss_terms(oi, o[5], o[6], o[7], io.eps_clip, red + 4 * TIDX(), red + 4 * SPW + TIDX());
+        loss_terms(oi, o[5], o[6], o[7], eps_clip, red + 4 * TIDX(), red + 4 * SPW + TIDX());
     }
     __syncthreads();
     loss_block_sums(TID_C red, io.fpart, io.vpart, blockIdx.x);
@@ -719,6 +720,9 @@ __device__ void heads_bwd(Smem& sm, const float* __restrict__ P, const BwdIO& io
         oa = ld4(io.smp + (size_t)(b0 + tid_x()) * 8);
         ob = ld4(io.smp + (size_t)(b0 + tid_x()) * 8 + 4);
     }
+    // the scheduled values (BwdIO::hyper), with the other global inputs of the prologue
+    const float eps_clip = hyper_f32(io.hyper, UAVHIP_HP_EPS_CLIP, io.eps_clip);
+    const float entropy_coef = hyper_f32(io.hyper, UAVHIP_HP_ENTROPY_COEF, io.entropy_coef);
     float tot0, tot1, tot2, tot3;
     if (io.fpart) {
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
@@ -745,7 +749,7 @@ __device__ void heads_bwd(Smem& sm, const float* __restrict__ P, const BwdIO& io
         const CatVals c = categorical(o[5], o[6]);
         const float logp = act ? c.lc1 : c.lc0;
         const float ratio = expf(logp - o[1]);
-        const float A = o[4], lo = 1.f - io.eps_clip, hi = 1.f + io.eps_clip;
+        const float A = o[4], lo = 1.f - eps_clip, hi = 1.f + eps_clip;
         const float s1 = ratio * A;
         const float s2 = fminf(fmaxf(ratio, lo), hi) * A;
         const float gmin = -ginv;  // d(-mean(min)) / d min_i (x gscale)
@@ -753,7 +757,7 @@ __device__ void heads_bwd(Smem& sm, const float* __restrict__ P, const BwdIO& io
         const float g2 = s2 < s1 ? gmin : (s1 == s2 ? 0.5f * gmin : 0.f);
         const float gr = g1 * A + ((ratio >= lo && ratio <= hi) ? g2 * A : 0.f);
         const float glogp = gr * ratio;
-        const float gent = -io.entropy_coef * ginv;
+        const float gent = -entropy_coef * ginv;
         // back through lc = log(clamp(p)), ent = -sum(lc * p), p = y / s, s = y0 + y1, y = softmax
         float glc0 = -gent * c.p0, glc1 = -gent * c.p1;
         if (act) glc1 += glogp; else glc0 += glogp;
@@ -767,13 +771,13 @@ __device__ void heads_bwd(Smem& sm, const float* __restrict__ P, const BwdIO& io
         const float L1 = tot1 * inv, L2 = tot2 * inv;
         const float v = o[7], R = o[3], ov = o[2];
         const float dv = v - ov;
-        const float vc = ov + fminf(fmaxf(dv, -io.eps_clip), io.eps_clip);
+        const float vc = ov + fminf(fmaxf(dv, -eps_clip), eps_clip);
         const float w1 = L1 > L2 ? 1.f : (L1 == L2 ? 0.5f : 0.f);
         const float w2 = L2 > L1 ? 1.f : (L1 == L2 ? 0.5f : 0.f);
         gs[4 * p + 0] = pad ? 0.f : c.y0 * (gy0 - dot);
         gs[4 * p + 1] = pad ? 0.f : c.y1 * (gy1 - dot);
         gs[4 * p + 2] = pad ? 0.f : io.value_coef * (w1 * 2.f * (v - R) * ginv_c +
-                                         ((dv >= -io.eps_clip && dv <= io.eps_clip) ? w2 * 2.f * (vc - R) * ginv_c : 0.f));
+                                         ((dv >= -eps_clip && dv <= eps_clip) ? w2 * 2.f * (vc - R) * ginv_c : 0.f));
         if (p == 0 && blk == 0 && role != 2 && io.stats) {
             io.stats[0] += (double)(-tot0 * inv);
             io.stats[1] += (double)fmaxf(L1, L2);

@@ -114,8 +114,9 @@ __device__ void loss_partials(TID_F Smem& sm, const TrainIO& io, int b0) {
         o[5] = l0;
         o[6] = l1;
         o[7] = v;
+        const float eps_clip = hyper_f32(io.hyper, UAVHIP_HP_EPS_CLIP, io.eps_clip);
         const float oi[5] = {o[0], o[1], o[2], o[3], o[4]};
-        loss_terms(oi, l0, l1, v, io.eps_clip, red + 4 * p, red + 4 * SPW + p);
+        loss_terms(oi, l0, l1, v, eps_clip, red + 4 * p, red + 4 * SPW + p);
     }
     __syncthreads();
     loss_block_sums(TID_C red, io.fpart, io.vpart, b0 / SPW);

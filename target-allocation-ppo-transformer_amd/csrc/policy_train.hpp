@@ -7,10 +7,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/uavhip.h"  // uavhip_ppo_hyper
 #include "policy_layout.hpp"
 
 namespace uavhip {
 namespace pol {
+
+// A scheduled hyper-parameter of the step (uavhip.h uavhip_ppo_hyper): from the step's device buffer
+// when it has one (uavhip_ppo_step_hyper: read when the kernel runs, so a captured graph follows the
+// buffer; one double -> float rounding), else the by-value field. The pointer is a kernel argument
+// and the index a constant: one wave-uniform load.
+__device__ __forceinline__ float hyper_f32(const double* hyper, int i, float by_value) {
+    return hyper ? (float)hyper[i] : by_value;
+}
 
 struct TrainLayerIO {
     float *qkv, *o, *xhat1, *rstd1, *h1, *u, *xhat2, *rstd2, *h2;
@@ -35,6 +44,7 @@ struct TrainIO {
                                  // sum (v-R)^2, sum (vc-R)^2, sum entropy (smp[5..7] = logits, value)
     float* vpart;                // [Bm/16] per-workgroup max(|v - R|, |vc - R|) (BwdIO::vpart)
     float eps_clip;
+    const double* hyper;         // nullable: [UAVHIP_HP_COUNT] device values that replace eps_clip (hyper_f32)
     // trunk split (small minibatches, 2 Bm/16 <= the CU count): workgroups [0, split) run the
     // actor trunk + head, [split, 2 split) the critic trunk + head of the same 16-sample blocks
     // (the two trunks are independent until the loss); the loss partials then come from
@@ -76,6 +86,7 @@ struct BwdIO {
     float* hpart;            // [Bm/16][kHeadPart] head.2 weight / bias gradient partials
     double* stats;           // += loss_actor, loss_critic, entropy, 1 (workgroup 0)
     float eps_clip, value_coef, entropy_coef;
+    const double* hyper;     // nullable: [UAVHIP_HP_COUNT] device values that replace eps_clip / entropy_coef
     int Bg;                  // samples in the global minibatch
     // every gradient the backward writes is pre-scaled by gscale = the power of two >= Bg (the
     // loss's 1/Bg folded in as gscale/Bg, exact): per-sample gradients O(1) instead of O(1/Bg), so

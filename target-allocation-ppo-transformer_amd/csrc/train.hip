@@ -97,6 +97,7 @@ using pol::kEmbPart;
 // (torch's non-capturable single-tensor Adam), each coefficient rounded to float once.
 struct AdamHyper {
     double lr_actor, lr_critic, beta1, beta2;
+    const double* hyper;  // nullable: the learning rates from device memory (uavhip_ppo_step_hyper), as doubles
 };
 struct AdamScalars {
     float nss_a, nss_c, bc2s, pad;  // -lr / (1 - b1^t) per group, sqrt(1 - b2^t)
@@ -104,8 +105,10 @@ struct AdamScalars {
 __device__ __forceinline__ void adam_advance(double* __restrict__ step, const AdamHyper& h, AdamScalars* __restrict__ sc) {
     const double t = step[0] + 1.0;
     step[0] = t;
+    const double lr_actor = h.hyper ? h.hyper[UAVHIP_HP_LR_ACTOR] : h.lr_actor;
+    const double lr_critic = h.hyper ? h.hyper[UAVHIP_HP_LR_CRITIC] : h.lr_critic;
     const double bc1 = 1.0 - pow(h.beta1, t), bc2 = 1.0 - pow(h.beta2, t);
-    *sc = AdamScalars{(float)(-(h.lr_actor / bc1)), (float)(-(h.lr_critic / bc1)), (float)sqrt(bc2), 0.f};
+    *sc = AdamScalars{(float)(-(lr_actor / bc1)), (float)(-(lr_critic / bc1)), (float)sqrt(bc2), 0.f};
 }
 
 // grads[dst + i] = sum_p src[p * part_stride + i] for each segment; block partial sums of g^2.
@@ -544,7 +547,9 @@ inline float grad_prescale(int flags, int Bg) {
 }
 
 inline const float* prm(const uavhip_ppo* c, int i) { return c->params + kOffs.o[i]; }
-inline AdamHyper adam_hyper(const uavhip_ppo* c) { return AdamHyper{c->lr_actor, c->lr_critic, c->beta1, c->beta2}; }
+inline AdamHyper adam_hyper(const uavhip_ppo* c, const double* hyper) {
+    return AdamHyper{c->lr_actor, c->lr_critic, c->beta1, c->beta2, hyper};
+}
 
 // Position split (K7) for this minibatch size (UAVHIP_PPO_NO_POS_SPLIT turns it off).
 inline bool pos_split(int flags, int Bm) { return pol::ps_capable(Bm) && !(flags & UAVHIP_PPO_NO_POS_SPLIT); }
@@ -587,28 +592,29 @@ extern "C" int64_t uavhip_ppo_workspace_floats(int32_t minibatch) {
         if (rc_) return rc_; \
     } while (0)
 
-static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int Bg, double* step, int* n_sq,
-                        bool fused_sums);
+static int ppo_backward(const uavhip_ppo* c, const double* hyper, const Plan& p, hipStream_t st, int Bg, double* step,
+                        int* n_sq, bool fused_sums);
 
-extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const int8_t* actions,
-                               const float* old_logp, const float* old_values, const float* returns,
-                               const float* advantages, const int32_t* idx, int32_t phases, uavhip_stream_t stream) {
+// The step behind both entry points; `fn` names the one called in the error messages.
+static int ppo_step(const char* fn, const uavhip_ppo* c, const double* hyper, const float* states,
+                    const int8_t* actions, const float* old_logp, const float* old_values, const float* returns,
+                    const float* advantages, const int32_t* idx, int32_t phases, uavhip_stream_t stream) {
     const bool fwd = phases & UAVHIP_PPO_FORWARD, bwd = phases & UAVHIP_PPO_BACKWARD, upd = phases & UAVHIP_PPO_UPDATE;
     if (!c || !c->params || !c->grads || !c->workspace || !c->loss_sums ||
         ((fwd || bwd) && (!states || !actions || !old_logp || !old_values || !returns || !advantages || !idx))) {
-        set_error("uavhip_ppo_step: NULL pointer");
+        set_error("%s: NULL pointer", fn);
         return UAVHIP_EINVAL;
     }
     const int Bg = c->global_minibatch > 0 ? c->global_minibatch : c->minibatch;
     if (c->minibatch <= 0 || c->minibatch % 64 || Bg < c->minibatch || c->n_floats != kOffs.o[kNumParams] ||
         (phases & UAVHIP_PPO_FULL) == 0 || (phases & ~(UAVHIP_PPO_FULL | UAVHIP_PPO_PACKED)) ||
         (upd && (!c->adam_m || !c->adam_v || !c->adam_step))) {
-        set_error("uavhip_ppo_step: minibatch %d (multiple of 64), global %d, n_floats %d (expected %d), phases %d",
+        set_error("%s: minibatch %d (multiple of 64), global %d, n_floats %d (expected %d), phases %d", fn,
                   c->minibatch, Bg, c->n_floats, kOffs.o[kNumParams], phases);
         return UAVHIP_EINVAL;
     }
     if (c->flags & ~UAVHIP_PPO_FLAGS_ALL) {
-        set_error("uavhip_ppo_step: flags 0x%x has bits outside UAVHIP_PPO_FLAGS_ALL (0x%x)", c->flags,
+        set_error("%s: flags 0x%x has bits outside UAVHIP_PPO_FLAGS_ALL (0x%x)", fn, c->flags,
                   UAVHIP_PPO_FLAGS_ALL);
         return UAVHIP_EINVAL;
     }
@@ -646,6 +652,7 @@ extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const i
         io.fpart = p.fpart;
         io.vpart = p.vpart;
         io.eps_clip = c->eps_clip;
+        io.hyper = hyper;
         if (pos_split(c->flags, Bm)) {  // K7: F1 / F2 / F3 (F3 writes the loss partials)
             TR_CHECK(pol::policy_forward_ps(p.packed, states, io, Bm, st));
         } else {
@@ -662,11 +669,11 @@ extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const i
     // single-GPU FULL step: the gradient reduction leaves the g^2 partials of the final grads;
     // otherwise (UPDATE after an all-reduce of grads) k_grad_norm computes them
     int n_sq = kSqBlocks;
-    if (bwd) TR_CHECK(ppo_backward(c, p, st, Bg, upd ? c->adam_step : nullptr, &n_sq, fwd));
+    if (bwd) TR_CHECK(ppo_backward(c, hyper, p, st, Bg, upd ? c->adam_step : nullptr, &n_sq, fwd));
     if (upd) {
         if (!bwd) {
             hipLaunchKernelGGL(k_grad_norm, dim3(kSqBlocks), dim3(256), 0, st, c->grads, c->n_floats, p.sq_part,
-                               c->adam_step, adam_hyper(c), p.adam_sc, p.packed + kRangeOff + kRgMax);
+                               c->adam_step, adam_hyper(c, hyper), p.adam_sc, p.packed + kRangeOff + kRgMax);
             TR_CHECK(check_launch("k_grad_norm"));
         }
         AdamArgs aa{c->params, c->grads, c->adam_m, c->adam_v, p.adam_sc, p.sq_part, n_sq, c->beta1, c->beta2,
@@ -677,9 +684,24 @@ extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const i
     return UAVHIP_OK;
 }
 
+extern "C" int uavhip_ppo_step(const uavhip_ppo* c, const float* states, const int8_t* actions,
+                               const float* old_logp, const float* old_values, const float* returns,
+                               const float* advantages, const int32_t* idx, int32_t phases, uavhip_stream_t stream) {
+    return ppo_step("uavhip_ppo_step", c, nullptr, states, actions, old_logp, old_values, returns, advantages, idx,
+                    phases, stream);
+}
+
+extern "C" int uavhip_ppo_step_hyper(const uavhip_ppo* c, const double* hyper, const float* states,
+                                     const int8_t* actions, const float* old_logp, const float* old_values,
+                                     const float* returns, const float* advantages, const int32_t* idx,
+                                     int32_t phases, uavhip_stream_t stream) {
+    return ppo_step("uavhip_ppo_step_hyper", c, hyper, states, actions, old_logp, old_values, returns, advantages,
+                    idx, phases, stream);
+}
+
 // Backward + weight gradients of one minibatch (the workspace holds the forward's activations).
-static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int Bg, double* step, int* n_sq,
-                        bool fused_sums) {
+static int ppo_backward(const uavhip_ppo* c, const double* hyper, const Plan& p, hipStream_t st, int Bg, double* step,
+                        int* n_sq, bool fused_sums) {
     const int Bm = p.Bm, R = p.R, nblk = Bm / kHeadSamples;
     const LayerBufs &A = p.la, &C0 = p.lc0, &C1 = p.lc1;
     const int ta = kActorTrunk, tc = kCriticTrunk;
@@ -706,6 +728,7 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
         io.eps_clip = c->eps_clip;
         io.value_coef = c->value_coef;
         io.entropy_coef = c->entropy_coef;
+        io.hyper = hyper;
         io.Bg = Bg;
         io.gscale = grad_prescale(c->flags, Bg);
         io.vpart = p.vpart;
@@ -861,7 +884,7 @@ static int ppo_backward(const uavhip_ppo* c, const Plan& p, hipStream_t st, int 
     }
     // padding floats between parameters stay zero
     hipLaunchKernelGGL(k_reduce_grads, dim3(seg_blocks), dim3(256), 0, st, sb, c->grads, p.sq_part, step,
-                       adam_hyper(c), p.adam_sc, 1.0f / grad_prescale(c->flags, Bg), static_cast<const float*>(p.gsc),
+                       adam_hyper(c, hyper), p.adam_sc, 1.0f / grad_prescale(c->flags, Bg), static_cast<const float*>(p.gsc),
                        kOffs.o[kCriticTrunk], step ? p.packed + kRangeOff + kRgMax : nullptr);
     *n_sq = seg_blocks;
     return check_launch("k_reduce_grads");

@@ -41,6 +41,9 @@ PPO_FORWARD, PPO_BACKWARD, PPO_UPDATE, PPO_FULL, PPO_PACKED = 1, 2, 4, 7, 8
 # uavhip_ppo.flags bits (0 = the measured defaults)
 PPO_NO_POS_SPLIT, PPO_NO_TRUNK_SPLIT, PPO_WGRAD_STREAM_K = 1, 2, 4
 PPO_FIXED_ORDER_FWD, PPO_FIXED_ORDER_BWD, PPO_NO_GRAD_PRESCALE = 8, 16, 32
+# enum uavhip_ppo_hyper: the device buffer of uavhip_ppo_step_hyper, [HP_COUNT] doubles
+HP = dict(LR_ACTOR=0, LR_CRITIC=1, ENTROPY_COEF=2, EPS_CLIP=3)
+HP_COUNT = 4
 EP = dict(ENV=0, EPISODE=1, STEPS=2, REWARD=3, Q0=4, J_SUM=5, MAX_COV=6, ACTION1=7, VALID=8, PDMG_SUM=9,
           PFINAL_SUM=10, ASSIGN_STEPS=11)
 EP_COUNT = 12
@@ -131,6 +134,8 @@ _SIGS = {
                                            _vp, _vp, _vp, _vp]),
     "uavhip_ppo_workspace_floats": (ctypes.c_int64, [_i32]),
     "uavhip_ppo_step": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "uavhip_ppo_step_hyper": (ctypes.c_int, [ctypes.POINTER(PPODesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
+                                             _vp]),
     "uavhip_ppo_diagnostics_partials": (_i32, [ctypes.c_int64]),
     "uavhip_ppo_diagnostics": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_double, _vp, _i32, _vp,
                                               _vp]),

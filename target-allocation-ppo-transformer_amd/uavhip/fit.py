@@ -29,9 +29,20 @@ from counters, the update is deterministic and graph replays equal direct launch
 continues bit for bit. The actor ring (rowproj) is rebuilt by every iteration's first step and is not
 saved.
 
-Out of scope: learning-rate / entropy schedules (the hyper-parameters are by-value kernel arguments
-baked into the epoch graph), more than one GPU, the reference's matplotlib curve and its per-episode
-CSV (uavhip.metrics.csv_rows stays available).
+Schedules: lr_schedule / entropy_schedule / clip_schedule ("constant", "linear", "cosine") scale both
+learning rates, the entropy coefficient and the clip range by schedule_value(kind, i, K, final_frac)
+for iteration i = 1, 2, ... over K = schedule_iterations iterations (held at final_frac from K on);
+lr_warmup ramps the learning rates up over the first W iterations. The values are constant within an
+iteration and written with FusedPPOTrainer.set_hyper before its update: the step reads them from
+device memory (uavhip_ppo_step_hyper), so the captured epoch graph is replayed unchanged. They are a
+function of the iteration number alone, so a resumed run continues bit for bit. A run without a
+schedule never calls set_hyper and writes the same progress lines as before.
+
+    TrainingRun(..., lr_schedule="linear", lr_final_frac=0.1, lr_warmup=5, schedule_iterations=300)
+    python -m uavhip.fit ... --lr-schedule cosine --entropy-schedule linear --schedule-iterations 300
+
+Out of scope: per-minibatch schedules and adaptive (KL-driven) rates, more than one GPU, the
+reference's matplotlib curve and its per-episode CSV (uavhip.metrics.csv_rows stays available).
 """
 import glob
 import json
@@ -60,6 +71,17 @@ HYPER_FIELDS = ("envs", "uavs", "targets", "horizon", "minibatch", "seed", "epoc
                 "lr_actor", "lr_critic", "eps_clip", "max_grad_norm", "value_coef", "entropy_coef", "gamma",
                 "gae_lambda")
 
+#: the schedule settings, saved as hp.* like HYPER_FIELDS; a state without them was written by an
+#: all-constant run (SCHEDULE_DEFAULTS), and --resume refuses a state where one differs
+SCHEDULE_FIELDS = ("lr_schedule", "entropy_schedule", "clip_schedule", "lr_final_frac", "entropy_final_frac",
+                   "clip_final_frac", "schedule_iterations", "lr_warmup")
+SCHEDULE_DEFAULTS = dict(lr_schedule="constant", entropy_schedule="constant", clip_schedule="constant",
+                         lr_final_frac=0.0, entropy_final_frac=0.0, clip_final_frac=1.0, schedule_iterations=0,
+                         lr_warmup=0)
+SCHEDULE_KINDS = ("constant", "linear", "cosine")
+#: progress.jsonl: the values the iteration's update used, after PROGRESS_FIELDS, in a scheduled run only
+SCHEDULE_PROGRESS_FIELDS = ("lr_actor", "lr_critic", "entropy_coef", "eps_clip")
+
 ENV_TENSORS = ("nh_final", "nh_pure", "t_cost", "n_lock", "assigned", "istate", "dstate", "window")
 KEEP_STATES = 2
 
@@ -76,6 +98,63 @@ def validate_shape(envs, uavs, targets, horizon, minibatch, eval_every=0):
     if eval_every > 0 and (uavs > 64 or targets > 64):
         raise ValueError(f"eval_every={eval_every}: the evaluation decodes with N, M <= 64 "
                          f"(uavs={uavs}, targets={targets}); pass eval_every=0")
+
+
+def schedule_value(kind, i, K, final_frac, warmup=0):
+    """The factor a scheduled hyper-parameter is multiplied by in iteration i = 1, 2, ... (Python
+    floats): 1 at i = 1, final_frac from i = K on, linear or half-cosine in between; for i <= warmup
+    the factor is also multiplied by i / warmup (the learning rates' ramp). "constant": 1 (K unused)."""
+    if kind not in SCHEDULE_KINDS:
+        raise ValueError(f"schedule kind {kind!r}: must be one of {SCHEDULE_KINDS}")
+    if i < 1:
+        raise ValueError(f"schedule iteration i={i}: iterations count from 1")
+    if kind == "constant":
+        s = 1.0
+    else:
+        if K < 2:
+            raise ValueError(f"schedule_iterations={K}: must be >= 2")
+        p = min(1.0, (i - 1) / (K - 1))
+        shape = 1.0 - p if kind == "linear" else 0.5 * (1.0 + math.cos(math.pi * p))
+        s = final_frac + (1.0 - final_frac) * shape
+    if i <= warmup:
+        s *= i / warmup
+    return s
+
+
+def validate_schedule(sched):
+    """The checks of the schedule arguments (a dict of SCHEDULE_FIELDS); each message names the argument."""
+    for k in ("lr_schedule", "entropy_schedule", "clip_schedule"):
+        if sched[k] not in SCHEDULE_KINDS:
+            raise ValueError(f"{k}={sched[k]!r}: must be one of {SCHEDULE_KINDS}")
+    for k in ("lr_final_frac", "entropy_final_frac", "clip_final_frac"):
+        if not (math.isfinite(sched[k]) and 0.0 <= sched[k] <= 1.0):
+            raise ValueError(f"{k}={sched[k]!r}: must lie in [0, 1]")
+    if sched["lr_warmup"] < 0:
+        raise ValueError(f"lr_warmup={sched['lr_warmup']}: must be >= 0 iterations")
+    shaped = any(sched[k] != "constant" for k in ("lr_schedule", "entropy_schedule", "clip_schedule"))
+    if shaped and sched["schedule_iterations"] < 2:
+        raise ValueError(f"schedule_iterations={sched['schedule_iterations']}: must be >= 2 when a schedule is not "
+                         "constant")
+    if not shaped and sched["schedule_iterations"] < 0:
+        raise ValueError(f"schedule_iterations={sched['schedule_iterations']}: must be >= 0")
+    if sched["clip_schedule"] != "constant" and sched["clip_final_frac"] <= 0.0:
+        raise ValueError(f"clip_final_frac={sched['clip_final_frac']!r}: the clip range must stay > 0")
+
+
+def scheduled(sched):
+    """Whether any value changes during the run (else the run never calls set_hyper)."""
+    return any(sched[k] != "constant" for k in ("lr_schedule", "entropy_schedule", "clip_schedule")) or \
+        sched["lr_warmup"] > 0
+
+
+def schedule_hyper(hyper, sched, i):
+    """The four values iteration i's update uses: {lr_actor, lr_critic, entropy_coef, eps_clip}."""
+    K = sched["schedule_iterations"]
+    s_lr = schedule_value(sched["lr_schedule"], i, K, sched["lr_final_frac"], sched["lr_warmup"])
+    s_ent = schedule_value(sched["entropy_schedule"], i, K, sched["entropy_final_frac"])
+    s_clip = schedule_value(sched["clip_schedule"], i, K, sched["clip_final_frac"])
+    return dict(lr_actor=hyper["lr_actor"] * s_lr, lr_critic=hyper["lr_critic"] * s_lr,
+                entropy_coef=hyper["entropy_coef"] * s_ent, eps_clip=hyper["eps_clip"] * s_clip)
 
 
 def save_state(state, path):
@@ -120,6 +199,11 @@ def check_compatible(state, hyper):
         if not same:
             raise ValueError(f"resume: {k} differs: the state was written with {k}={have!r}, this run has "
                              f"{k}={want!r}")
+    for k in SCHEDULE_FIELDS:  # absent (a state or a run from before the schedules): all-constant
+        have, want = state.get("hp." + k, SCHEDULE_DEFAULTS[k]), hyper.get(k, SCHEDULE_DEFAULTS[k])
+        if have != want:
+            raise ValueError(f"resume: {k} differs: the state was written with {k}={have!r}, this run has "
+                             f"{k}={want!r}")
 
 
 def _json_value(v):
@@ -137,14 +221,19 @@ class TrainingRun:
     def __init__(self, envs, uavs, targets, horizon, minibatch, out_dir, seed=0, epochs=None, target_kl=None,
                  diagnostics_every=1, eval_every=0, eval_scenes=1024, eval_seed=1, checkpoint_every=0,
                  reset_episodes=None, resume=None, lr_actor=None, lr_critic=None, eps_clip=None, max_grad_norm=None,
-                 value_coef=0.5, entropy_coef=0.01, device="cuda:0", init=None):
+                 value_coef=0.5, entropy_coef=0.01, device="cuda:0", init=None, lr_schedule="constant",
+                 entropy_schedule="constant", clip_schedule="constant", lr_final_frac=0.0, entropy_final_frac=0.0,
+                 clip_final_frac=1.0, schedule_iterations=0, lr_warmup=0):
         """target_kl: run the update epoch by epoch and drop the remaining epochs once the
         diagnostics' APPROX_KL exceeds it (None: one run() call of `epochs` epochs).
         resume: a state file, or a run directory (its latest state).
         init: a policy checkpoint (checkpoint.save_checkpoint's format, e.g. uavhip.imitate's
         final_model.pth) loaded into the seeded policy before training starts; everything else is
         seeded as without it. Not with resume (a state carries its own parameters), and not a
-        hyper-parameter: state files do not record it."""
+        hyper-parameter: state files do not record it.
+        lr_schedule / entropy_schedule / clip_schedule, *_final_frac, schedule_iterations, lr_warmup:
+        the schedules (module docstring, schedule_value); schedule_iterations is the schedule's own
+        length K, whatever number of iterations a fit() call runs."""
         if init is not None and resume is not None:
             raise ValueError("init and resume exclude each other: a resumed state carries its own parameters")
         self.init = None if init is None else str(init)
@@ -174,11 +263,20 @@ class TrainingRun:
             max_grad_norm=float(cfg.GRAD_NORM_CLIP if max_grad_norm is None else max_grad_norm),
             value_coef=float(value_coef), entropy_coef=float(entropy_coef), gamma=float(cfg.GAMMA),
             gae_lambda=float(cfg.GAE_LAMBDA))
+        self.schedule = dict(lr_schedule=str(lr_schedule), entropy_schedule=str(entropy_schedule),
+                             clip_schedule=str(clip_schedule), lr_final_frac=float(lr_final_frac),
+                             entropy_final_frac=float(entropy_final_frac), clip_final_frac=float(clip_final_frac),
+                             schedule_iterations=int(schedule_iterations), lr_warmup=int(lr_warmup))
+        validate_schedule(self.schedule)
+        self.scheduled = scheduled(self.schedule)
+        if self.scheduled:  # the base values the schedules scale go through set_hyper: its checks, up front
+            from .train import check_hyper
+            check_hyper(**{k: self.hyper[k] for k in SCHEDULE_PROGRESS_FIELDS})
         state = None
         if resume is not None:  # read and checked before anything is built
             self.resumed_from = latest_state(str(resume))
             state = load_state(self.resumed_from)
-            check_compatible(state, self.hyper)
+            check_compatible(state, {**self.hyper, **self.schedule})
         if not torch.cuda.is_available():
             raise RuntimeError("uavhip.fit trains on the GPU (HIP) only")
         self.device = torch.device(device)
@@ -187,6 +285,7 @@ class TrainingRun:
         self.best = float("-inf")
         self.wall_s = 0.0
         self.last = None       # the last progress line's fields
+        self.used = {k: self.hyper[k] for k in SCHEDULE_PROGRESS_FIELDS}  # the values of the current iteration's update
         self.phase_ms = {k: 0.0 for k in ("rollout", "update", "diagnostics", "drain", "eval", "files")}
         self._build()
         if state is not None:
@@ -247,7 +346,7 @@ class TrainingRun:
         s = {"format": STATE_FORMAT, "run.iteration": int(self.iteration), "run.best": float(self.best),
              "run.wall_s": float(self.wall_s), "engine.iteration": int(self.engine.iteration),
              "env.seed": int(self.env.desc.seed), "env.flags": int(self.env.desc.flags)}
-        for k, v in self.hyper.items():
+        for k, v in {**self.hyper, **self.schedule}.items():
             s["hp." + k] = v
         for k, v in self._device_tensors().items():
             s[k] = v.detach().cpu().clone()
@@ -307,7 +406,7 @@ class TrainingRun:
     # ------------------------------------------------------------------ one iteration
     def _diagnostics(self):
         from .ppo import update_diagnostics
-        return update_diagnostics(self.policy, *self.bufs[:5], eps_clip=self.hyper["eps_clip"], out=self.diag_out,
+        return update_diagnostics(self.policy, *self.bufs[:5], eps_clip=self.used["eps_clip"], out=self.diag_out,
                                   workspace=self.diag_ws)
 
     def _update(self):
@@ -348,6 +447,9 @@ class TrainingRun:
         traj = self.engine.collect()
         self.stats.update(traj)
         ev[1].record()
+        if self.scheduled:  # this iteration's values, for all its epochs and minibatches
+            self.used = schedule_hyper(self.hyper, self.schedule, it)
+            self.trainer.set_hyper(**self.used)
         la, lc, en, epochs_run, steps, diag_fresh = self._update()
         ev[2].record()
         want_diag = self.diagnostics_every > 0 and it % self.diagnostics_every == 0
@@ -366,6 +468,8 @@ class TrainingRun:
              "mean_ep_reward": mean(d["reward"]), "mean_ep_steps": mean(rec[:, _lib.EP["STEPS"]]),
              "mean_ep_J": mean(d["avg_J"]), "loss_actor": float(la), "loss_critic": float(lc), "entropy": float(en),
              "epochs_run": int(epochs_run), "optimizer_steps": int(steps), "wall_s": 0.0, "env_steps_per_s": 0.0}
+        if self.scheduled:
+            f.update((k, self.used[k]) for k in SCHEDULE_PROGRESS_FIELDS)
         if want_diag:
             f.update(zip(DIAG_FIELDS, self.diag_out.tolist()))
         score = f["mean_ep_reward"]
@@ -415,6 +519,8 @@ class TrainingRun:
                "best": _json_value(self.best),
                "phase_ms_per_iteration": {k: v / max(1, done) for k, v in self.phase_ms.items()},
                "last": None if self.last is None else {k: _json_value(v) for k, v in self.last.items()}}
+        if self.scheduled:
+            out["schedule"] = dict(self.schedule)
         return out
 
 
@@ -442,11 +548,24 @@ def main(argv=None):
     ap.add_argument("--resume", default=None, help="a state_it{K}.pt file, or a run directory (its latest state)")
     ap.add_argument("--init", default=None,
                     help="a policy checkpoint to start from (uavhip.imitate's final_model.pth); not with --resume")
+    for name in ("lr", "entropy", "clip"):
+        ap.add_argument(f"--{name}-schedule", choices=SCHEDULE_KINDS, default="constant",
+                        help=f"how the {dict(lr='learning rates', entropy='entropy coefficient', clip='clip range')[name]} "
+                             "change over --schedule-iterations")
+        ap.add_argument(f"--{name}-final-frac", type=float, default=SCHEDULE_DEFAULTS[f"{name}_final_frac"],
+                        help="the share of the base value the schedule ends at, in [0, 1]")
+    ap.add_argument("--schedule-iterations", type=int, default=0,
+                    help="the schedules' length K in iterations (>= 2; required with a schedule; not --iterations)")
+    ap.add_argument("--lr-warmup", type=int, default=0, help="ramp the learning rates up over this many iterations")
     a = ap.parse_args(argv)
     run = TrainingRun(a.envs, a.uavs, a.targets, a.horizon, a.minibatch, a.out, seed=a.seed, epochs=a.epochs,
                       target_kl=a.target_kl, diagnostics_every=a.diagnostics_every, eval_every=a.eval_every,
                       eval_scenes=a.eval_scenes, eval_seed=a.eval_seed, checkpoint_every=a.checkpoint_every,
-                      reset_episodes=a.reset_episodes, resume=a.resume, init=a.init)
+                      reset_episodes=a.reset_episodes, resume=a.resume, init=a.init, lr_schedule=a.lr_schedule,
+                      entropy_schedule=a.entropy_schedule, clip_schedule=a.clip_schedule,
+                      lr_final_frac=a.lr_final_frac, entropy_final_frac=a.entropy_final_frac,
+                      clip_final_frac=a.clip_final_frac, schedule_iterations=a.schedule_iterations,
+                      lr_warmup=a.lr_warmup)
     print(json.dumps(run.fit(a.iterations)))
 
 

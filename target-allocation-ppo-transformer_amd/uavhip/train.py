@@ -26,6 +26,7 @@ group ("nccl") the collectives are captured with the kernels: a data-parallel ep
 buffers is one hipGraph replay like a single-GPU one (gloo's collectives run on the host: eager).
 """
 import ctypes
+import math
 
 import torch
 
@@ -33,6 +34,26 @@ from . import _lib
 from ._lib import LIB, check, ptr, stream_handle
 from .config import cfg
 from .policy import layout
+
+
+def check_hyper(lr_actor=None, lr_critic=None, entropy_coef=None, eps_clip=None):
+    """Validate the values set_hyper takes (None: not given) -> {name: float}. Host only: the device
+    does not validate the buffer (include/uavhip.h uavhip_ppo_step_hyper)."""
+    out = {}
+    for name, v, positive in (("lr_actor", lr_actor, False), ("lr_critic", lr_critic, False),
+                              ("entropy_coef", entropy_coef, False), ("eps_clip", eps_clip, True)):
+        if v is None:
+            continue
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number, got {v!r}") from None
+        if not math.isfinite(f):
+            raise ValueError(f"{name} must be finite, got {v!r}")
+        if f <= 0.0 if positive else f < 0.0:
+            raise ValueError(f"{name} must be {'> 0' if positive else '>= 0'}, got {v!r}")
+        out[name] = f
+    return out
 
 
 class FusedPPOTrainer:
@@ -98,6 +119,34 @@ class FusedPPOTrainer:
         self._store = None  # stage(): the trainer's own trajectory buffers
         self._cap = 0
         self.n_local = None  # set_shard(): rows of this rank's shard
+        self.hyper = None   # set_hyper(): the device [HP_COUNT] f64 buffer the step reads its schedule values from
+        self._hyper_host = None
+
+    def set_hyper(self, lr_actor=None, lr_critic=None, entropy_coef=None, eps_clip=None):
+        """Change the learning rates, the entropy coefficient or the clip range for the steps that
+        follow (None: keep). The first call moves the step to uavhip_ppo_step_hyper: the four values
+        live in a device buffer (initialised from the descriptor's) that the kernels read when they
+        run, so a captured epoch graph is replayed across changes without a re-capture; the graphs
+        captured before it are dropped. Every call writes the given values stream-ordered on the
+        current stream through a pinned staging tensor (no synchronisation; never inside a
+        capture). A trainer that never calls this runs uavhip_ppo_step as before."""
+        vals = check_hyper(lr_actor, lr_critic, entropy_coef, eps_clip)  # before any device work
+        if self.hyper is None:
+            d = self.desc
+            # the floats widened to double: (float)hyper[i] gives the descriptor's value back bit for bit
+            host = torch.tensor([d.lr_actor, d.lr_critic, d.entropy_coef, d.eps_clip], dtype=torch.float64)
+            self._hyper_host = host.pin_memory()
+            self.hyper = torch.empty(_lib.HP_COUNT, dtype=torch.float64, device=self.device)
+            self.graphs = {}  # captured on uavhip_ppo_step: by-value arguments
+        elif not vals:
+            return
+        else:
+            # the staging tensor may still feed an earlier copy: a new one per write, the old one is
+            # kept alive by the caching host allocator until that copy has run
+            self._hyper_host = self._hyper_host.clone().pin_memory()
+        for name, v in vals.items():
+            self._hyper_host[_lib.HP[name.upper()]] = v
+        self.hyper.copy_(self._hyper_host, non_blocking=True)
 
     def _restore_rows(self):
         """Back to minibatch / world rows per step after a set_shard() run resized the workspace to
@@ -181,11 +230,17 @@ class FusedPPOTrainer:
         self.n_local = None
 
     def step(self, phases=_lib.PPO_FULL, idx=None):
-        """uavhip_ppo_step phases (bit mask) on this rank's rows idx (default self.idx)."""
+        """uavhip_ppo_step phases (bit mask) on this rank's rows idx (default self.idx); after
+        set_hyper, uavhip_ppo_step_hyper on the trainer's device values."""
         s, a, lp, v, r, adv = self.bufs
         idx = self.idx if idx is None else idx
-        check(LIB.uavhip_ppo_step(self.desc, ptr(s), ptr(a), ptr(lp), ptr(v), ptr(r), ptr(adv), ptr(idx),
-                                  int(phases), stream_handle()), "uavhip_ppo_step")
+        if self.hyper is None:
+            check(LIB.uavhip_ppo_step(self.desc, ptr(s), ptr(a), ptr(lp), ptr(v), ptr(r), ptr(adv), ptr(idx),
+                                      int(phases), stream_handle()), "uavhip_ppo_step")
+        else:
+            check(LIB.uavhip_ppo_step_hyper(self.desc, ptr(self.hyper), ptr(s), ptr(a), ptr(lp), ptr(v), ptr(r),
+                                            ptr(adv), ptr(idx), int(phases), stream_handle()),
+                  "uavhip_ppo_step_hyper")
 
     def _rows(self, perm, b):
         """This rank's rows of global minibatch b of the permutation perm (a view)."""
