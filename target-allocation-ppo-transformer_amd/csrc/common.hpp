@@ -20,6 +20,14 @@ namespace uavhip {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 int validate_env(const uavhip_env* env, bool need_state);  // env.hip: descriptor checks of the C ABI
+int validate_env_for(const char* fn, const uavhip_env* env, bool need_state);  // the same, "fn: " in front of the message
+int require_f32_obs(const char* fn, const uavhip_env* env);  // env.hip: UAVHIP_EINVAL under UAVHIP_ENV_OBS_F16
+// The uavhip_*_trace getters of a TRACE build: the first min(n, total) stamps of device buffer `symbol`
+template <class T>
+int copy_trace(const T& symbol, int total, unsigned long long* out, int n) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(symbol), sizeof(unsigned long long) * (n < total ? n : total), 0,
+                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
 
 // ------------------------------------------------------------------ wave helpers
 constexpr int kWave = 64;

@@ -8,6 +8,8 @@
 //  * K2 keeps the whole env state in registers across T fused steps; T = 1 is the per-step
 //    rollout call, T > 1 the env-only multi-step launch (BASELINE config 2). It never generates a
 //    scene itself (register budget: 4 waves / SIMD); full resets flip to the spare buffer.
+#include <cstdio>
+
 #include "env_device.hpp"
 #include "env_group.hpp"
 #include "env_replay.hpp"
@@ -241,22 +243,27 @@ int validate_env(const uavhip_env* env, bool need_state) {
     }
     return UAVHIP_OK;
 }
+int validate_env_for(const char* fn, const uavhip_env* env, bool need_state) {
+    const int rc = validate_env(env, need_state);
+    if (rc) {
+        char why[256];
+        snprintf(why, sizeof why, "%s", uavhip_last_error());
+        set_error("%s: %s", fn, why);
+    }
+    return rc;
+}
+int require_f32_obs(const char* fn, const uavhip_env* env) {
+    if (!(env->flags & UAVHIP_ENV_OBS_F16)) return UAVHIP_OK;
+    set_error("%s: f32 observations only (the env has UAVHIP_ENV_OBS_F16 set)", fn);
+    return UAVHIP_EINVAL;
+}
 namespace {
 int validate(const uavhip_env* env, bool need_state) { return validate_env(env, need_state); }
-inline int wave_grid(int E) { return (E + kWavesPerBlock - 1) / kWavesPerBlock; }
 }  // namespace
 
 }  // namespace uavhip
 
 using namespace uavhip;
-
-#define UAVHIP_LAUNCH_TPL(kern, ...)                                                                       \
-    do {                                                                                                   \
-        if (env->M <= kWave)                                                                               \
-            hipLaunchKernelGGL(kern<1>, dim3(wave_grid(env->E)), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); \
-        else                                                                                               \
-            hipLaunchKernelGGL(kern<2>, dim3(wave_grid(env->E)), dim3(kBlock), 0, (hipStream_t)stream, __VA_ARGS__); \
-    } while (0)
 
 extern "C" int uavhip_score_pairs(const uavhip_env* env, const uint8_t* mask, uavhip_stream_t stream) {
     int rc = validate(env, false);
@@ -268,7 +275,7 @@ extern "C" int uavhip_score_pairs(const uavhip_env* env, const uint8_t* mask, ua
 extern "C" int uavhip_scene_generate(const uavhip_env* env, const uint8_t* mask, uavhip_stream_t stream) {
     int rc = validate(env, false);
     if (rc) return rc;
-    UAVHIP_LAUNCH_TPL(k_scene_generate, *env, mask);
+    UAVHIP_WAVE_LAUNCH(env, k_scene_generate<TPL>, 0, stream, *env, mask);
     return check_launch("k_scene_generate");
 }
 
@@ -276,7 +283,7 @@ extern "C" int uavhip_scene_refresh(const uavhip_env* env, uavhip_stream_t strea
     int rc = validate(env, false);
     if (rc) return rc;
     if (env->scene_buffers != 2) return UAVHIP_OK;
-    UAVHIP_LAUNCH_TPL(k_scene_refresh, *env);
+    UAVHIP_WAVE_LAUNCH(env, k_scene_refresh<TPL>, 0, stream, *env);
     return check_launch("k_scene_refresh");
 }
 
@@ -284,15 +291,13 @@ extern "C" int uavhip_env_reset(const uavhip_env* env, const uint8_t* mask, int3
                                 uavhip_stream_t stream) {
     int rc = validate(env, true);
     if (rc) return rc;
-    UAVHIP_LAUNCH_TPL(k_env_reset, *env, mask, (int)episode, obs_out);
+    UAVHIP_WAVE_LAUNCH(env, k_env_reset<TPL>, 0, stream, *env, mask, (int)episode, obs_out);
     return check_launch("k_env_reset");
 }
 
 #ifdef UAVHIP_POLICY_TRACE
 extern "C" int uavhip_env_trace(unsigned long long* out, int n) {  // k_env_replay phase sums (TRACE build)
-    const int total = envrep::kTraceEnvs * envrep::kTracePhases;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(envrep::g_etrace), sizeof(unsigned long long) * (n < total ? n : total),
-                               0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    return copy_trace(envrep::g_etrace, envrep::kTraceEnvs * envrep::kTracePhases, out, n);
 }
 #endif
 
@@ -303,7 +308,7 @@ extern "C" int uavhip_env_step(const uavhip_env* env, const int8_t* actions, int
     if (!actions || T <= 0) { set_error("actions NULL or T <= 0 (T=%d)", T); return UAVHIP_EINVAL; }
     const size_t tab = (size_t)kWavesPerBlock * env->N * env->M * sizeof(double);
     const bool lt = T >= kTableMinSteps && tab <= kTableMaxBytes;
-    const dim3 grid(wave_grid(env->E)), block(kBlock);
+    const dim3 grid((env->E + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
     // K2r (env_replay.hpp): with omega == 0 the walk is a function of the actions; replay it. Fastest
     // wherever it applies (T = 256, all outputs, G env-steps/s on MI355X: 1024 x 8 x 16 3.07 vs K2g
@@ -338,12 +343,11 @@ extern "C" int uavhip_env_step(const uavhip_env* env, const int8_t* actions, int
     // (the single-step load order with prefetched next-pair candidates, load_regs<TPL, true>, runs
     // inside the fused rollout launch; instantiating it here as well slowed the multi-step kernels
     // of this code object by ~9 % with byte-identical machine code for them: code placement)
-    if (env->M <= kWave) {
-        if (lt) hipLaunchKernelGGL((k_env_step<1, true>), grid, block, tab, st, *env, actions, (int)T, (int)auto_reset, obs_out, reward, done, info);
-        else hipLaunchKernelGGL((k_env_step<1, false>), grid, block, 0, st, *env, actions, (int)T, (int)auto_reset, obs_out, reward, done, info);
-    } else {
-        if (lt) hipLaunchKernelGGL((k_env_step<2, true>), grid, block, tab, st, *env, actions, (int)T, (int)auto_reset, obs_out, reward, done, info);
-        else hipLaunchKernelGGL((k_env_step<2, false>), grid, block, 0, st, *env, actions, (int)T, (int)auto_reset, obs_out, reward, done, info);
-    }
+    // (TPL outside, the table inside: the order the four instantiations are emitted in stays as it was)
+    UAVHIP_WITH_TPL(env->M,
+                    if (lt) hipLaunchKernelGGL((k_env_step<TPL, true>), grid, block, tab, st, *env, actions, (int)T,
+                                               (int)auto_reset, obs_out, reward, done, info);
+                    else hipLaunchKernelGGL((k_env_step<TPL, false>), grid, block, 0, st, *env, actions, (int)T,
+                                            (int)auto_reset, obs_out, reward, done, info));
     return check_launch("k_env_step");
 }

@@ -698,3 +698,22 @@ __device__ void step_once(EnvRegs<TPL>& R, const uavhip_env& env, int e, int lan
 
 }  // namespace envdev
 }  // namespace uavhip
+
+// ------------------------------------------------------------------ host: the TPL dispatch
+// TPL, the targets a lane owns, follows from the env's M: 1 for M <= 64, else 2. UAVHIP_WITH_TPL runs
+// its statement with TPL bound to that constant. UAVHIP_WAVE_LAUNCH launches `kern` (an expression in
+// TPL, in parentheses when it has a comma) for all of `env`: one wave per env, kWavesPerBlock (the
+// including file's, with its kBlock) per workgroup.
+#define UAVHIP_WITH_TPL(M, ...)       \
+    do {                              \
+        if ((M) <= ::uavhip::kWave) { \
+            constexpr int TPL = 1;    \
+            __VA_ARGS__;              \
+        } else {                      \
+            constexpr int TPL = 2;    \
+            __VA_ARGS__;              \
+        }                             \
+    } while (0)
+#define UAVHIP_WAVE_LAUNCH(env, kern, lds, stream, ...)                                                            \
+    UAVHIP_WITH_TPL((env)->M, hipLaunchKernelGGL((kern), dim3(((env)->E + kWavesPerBlock - 1) / kWavesPerBlock), \
+                                                 dim3(kBlock), lds, (hipStream_t)(stream), __VA_ARGS__))

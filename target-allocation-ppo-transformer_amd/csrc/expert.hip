@@ -17,8 +17,6 @@
 // While the pointer walks one UAV's targets the lock set changes only on the assign that ends the
 // visit: g[] (one coalesced row of p_dmg[u][:]) and its exclusive suffix maximum (a reverse wave
 // scan) are formed once per visit and the step reads two lanes of them.
-#include <cstdio>
-
 #include "env_device.hpp"
 
 #pragma clang fp contract(off)
@@ -157,12 +155,7 @@ extern "C" int uavhip_expert_steps(const uavhip_env* env, const int8_t* actions_
                                    double* reward, uint8_t* done, int32_t* steps, uint8_t* finished, double* ep_return,
                                    int32_t* stats, uavhip_stream_t stream) {
     using namespace uavhip;
-    if (const int rc = validate_env(env, true)) {
-        char why[256];
-        snprintf(why, sizeof why, "%s", uavhip_last_error());
-        set_error("uavhip_expert_steps: %s", why);
-        return rc;
-    }
+    if (const int rc = validate_env_for("uavhip_expert_steps", env, true)) return rc;
     if (n_max < 1 || !steps || !finished) {
         set_error("uavhip_expert_steps: need n_max=%d >= 1 and steps/finished non-NULL", n_max);
         return UAVHIP_EINVAL;
@@ -171,17 +164,8 @@ extern "C" int uavhip_expert_steps(const uavhip_env* env, const int8_t* actions_
         set_error("uavhip_expert_steps: follow needs actions_in (without a trace every env follows the expert)");
         return UAVHIP_EINVAL;
     }
-    if (env->flags & UAVHIP_ENV_OBS_F16) {
-        set_error("uavhip_expert_steps: f32 observations only (the env has UAVHIP_ENV_OBS_F16 set)");
-        return UAVHIP_EINVAL;
-    }
-    const dim3 grid((env->E + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlock);
-    const hipStream_t st = (hipStream_t)stream;
-    if (env->M <= kWave)
-        hipLaunchKernelGGL(k_expert_steps<1>, grid, block, 0, st, *env, actions_in, follow, (int)n_max, obs, actions,
-                           labels, margin, reward, done, steps, finished, ep_return, stats);
-    else
-        hipLaunchKernelGGL(k_expert_steps<2>, grid, block, 0, st, *env, actions_in, follow, (int)n_max, obs, actions,
-                           labels, margin, reward, done, steps, finished, ep_return, stats);
+    if (const int rc = require_f32_obs("uavhip_expert_steps", env)) return rc;
+    UAVHIP_WAVE_LAUNCH(env, k_expert_steps<TPL>, 0, stream, *env, actions_in, follow, (int)n_max, obs, actions, labels,
+                       margin, reward, done, steps, finished, ep_return, stats);
     return check_launch("k_expert_steps");
 }

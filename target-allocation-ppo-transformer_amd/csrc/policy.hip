@@ -33,6 +33,9 @@
 // kernels). This file holds what only this translation unit builds: the loss-partials and ring-fill
 // kernels, the training backward (K6), the position-split training kernels (K7), the weight pack /
 // split / range kernels, the launchers and the C ABI.
+#include <cstdarg>
+#include <cstdio>
+
 #include "policy_steps.hpp"  // policy_core.hpp, policy_encoder.hpp, policy_block.hpp, the multi-step launchers
 
 namespace uavhip {
@@ -1609,14 +1612,10 @@ extern "C" int32_t uavhip_policy_tiling(int32_t* kcols, int32_t max_params) {
 
 #ifdef UAVHIP_POLICY_TRACE
 extern "C" int uavhip_policy_trace(unsigned long long* out, int n) {
-    const int total = 256 * 2 * pol::kTraceSlots;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(pol::g_ptrace), sizeof(unsigned long long) * (n < total ? n : total), 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    return copy_trace(pol::g_ptrace, 256 * 2 * pol::kTraceSlots, out, n);
 }
 extern "C" int uavhip_policy_btrace(unsigned long long* out, int n) {  // k_policy_backward stamps
-    const int total = 256 * 2 * pol::kTraceSlots;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(pol::g_btrace), sizeof(unsigned long long) * (n < total ? n : total), 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    return copy_trace(pol::g_btrace, 256 * 2 * pol::kTraceSlots, out, n);
 }
 #endif
 
@@ -1662,11 +1661,13 @@ static int ring_fill(const uavhip_policy* policy, const float* states, const pol
     return check_launch("k_policy_rows_fill");
 }
 // The ring of a rows forward over B windows, for entry point `fn` (`count`: its name for B in the message,
-// "B" or "E"): the rowproj / step / 32-bit-offset check, the RowIO and the optional fill.
+// "B" or "E"): the rowproj / step / 32-bit-offset check, the RowIO and the optional fill. `also_ok`: what
+// the entry point requires besides, which `also` names in the message, after "NULL rowproj".
 static int ring_setup(const char* fn, const char* count, const uavhip_policy* policy, const float* states, int32_t B,
-                      float* rowproj, int32_t step, int32_t fill, uavhip_stream_t stream, pol::RowIO* rio) {
-    if (!rowproj || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
-        set_error("%s: NULL rowproj, step=%d < 0 or %s=%d above the ring's 32-bit offsets", fn, step, count, B);
+                      float* rowproj, int32_t step, int32_t fill, uavhip_stream_t stream, pol::RowIO* rio,
+                      const char* also = "", bool also_ok = true) {
+    if (!rowproj || !also_ok || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
+        set_error("%s: NULL rowproj%s, step=%d < 0 or %s=%d above the ring's 32-bit offsets", fn, also, step, count, B);
         return UAVHIP_EINVAL;
     }
     *rio = pol::RowIO{rowproj, (int)B, (int)step};
@@ -1694,18 +1695,45 @@ extern "C" int uavhip_policy_forward_rows(const uavhip_policy* policy, const flo
 extern "C" int uavhip_policy_value_rows(const uavhip_policy* policy, const float* states, int32_t B, float* rowproj,
                                         int32_t step, int32_t fill, float* value, uavhip_stream_t stream) {
     if (const int rc = check_policy("uavhip_policy_value_rows", policy, states, B)) return rc;
-    if (!rowproj || !value || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
-        set_error("uavhip_policy_value_rows: NULL rowproj / value, step=%d < 0 or B=%d above the ring's 32-bit offsets",
-                  step, B);
-        return UAVHIP_EINVAL;
-    }
+    pol::RowIO rio;
+    if (const int rc = ring_setup("uavhip_policy_value_rows", "B", policy, states, B, rowproj, step, fill, stream, &rio,
+                                  " / value", value != nullptr))
+        return rc;
     const int grid = (B + pol::SPW - 1) / pol::SPW;
-    const pol::RowIO rio{rowproj, (int)B, (int)step};
-    if (const int rc = ring_fill(policy, states, rio, fill, stream)) return rc;
     hipLaunchKernelGGL((pol::k_policy_forward<false, true, 0, true>), dim3(grid), dim3(pol::NTHR), 0, (hipStream_t)stream,
                        policy->weights, states, (int)B, nullptr, 0ull, 0ull, nullptr, nullptr, nullptr, value, nullptr,
                        nullptr, pol::TrainIO{}, rio, uavhip_env{}, pol::EnvOut{});
     return check_launch("k_policy_value_rows");
+}
+
+// What the four fused step entry points share ahead of their launch, for entry point `fn`: the env
+// (B = env->E windows), the policy, one env per wave (N, M <= 64), f32 observations where `f32_only`,
+// the entry point's own arguments (`args_ok`; `need`, a format and its values, names them in the
+// message), the ring on the windows at `states` (slot step & 1 of two where `two_slots`) and the floats
+// of B windows.
+struct StepSetup {
+    int32_t B;
+    long long stride;
+    pol::RowIO rio;
+};
+static int step_setup(StepSetup* su, const char* fn, const uavhip_policy* policy, const uavhip_env* env,
+                      const float* states, bool two_slots, float* rowproj, int32_t step, int32_t fill,
+                      uavhip_stream_t stream, bool f32_only, bool args_ok, const char* need, ...) {
+    if (const int rc = validate_env(env, true)) return rc;
+    su->B = env->E;
+    su->stride = (long long)su->B * pol::S * pol::IN;
+    if (const int rc = check_policy(fn, policy, states, su->B)) return rc;
+    if (env->N > 64 || env->M > 64 || (f32_only && require_f32_obs(fn, env)) || !args_ok) {
+        char rest[160];  // (require_f32_obs' own message is replaced by the entry point's, which names every condition)
+        va_list ap;
+        va_start(ap, need);
+        vsnprintf(rest, sizeof rest, need, ap);
+        va_end(ap);
+        set_error("%s: N=%d, M=%d must be <= 64%s%s", fn, env->N, env->M, f32_only ? ", observations f32" : "", rest);
+        return UAVHIP_EINVAL;
+    }
+    return ring_setup(fn, "E", policy, states + (two_slots ? (step & 1) * su->stride : 0), su->B, rowproj, step, fill,
+                      stream, &su->rio);
 }
 
 // Fused rollout step: uavhip_policy_forward_rows (sampling) + uavhip_env_step (T = 1) of env e
@@ -1715,19 +1743,14 @@ extern "C" int uavhip_rollout_step(const uavhip_policy* policy, const uavhip_env
                                    const uint64_t* offset_dev, int8_t* action_out, float* logp, float* value,
                                    int32_t auto_reset, float* obs_out, double* reward, uint8_t* done, double* info,
                                    uavhip_stream_t stream) {
-    if (const int rc = validate_env(env, true)) return rc;
-    const int32_t B = env->E;
-    if (const int rc = check_policy("uavhip_rollout_step", policy, states, B)) return rc;
-    if (env->N > 64 || env->M > 64 || !action_out || !obs_out || !reward || !done) {
-        set_error("uavhip_rollout_step: N=%d, M=%d must be <= 64 and action/obs/reward/done non-NULL", env->N, env->M);
-        return UAVHIP_EINVAL;
-    }
-    pol::RowIO rio;
-    if (const int rc = ring_setup("uavhip_rollout_step", "E", policy, states, B, rowproj, step, fill, stream, &rio)) return rc;
-    const int grid = (B + pol::SPW - 1) / pol::SPW;
+    StepSetup su;
+    if (const int rc = step_setup(&su, "uavhip_rollout_step", policy, env, states, false, rowproj, step, fill, stream, false,
+                                  action_out && obs_out && reward && done, " and action/obs/reward/done non-NULL"))
+        return rc;
+    const int grid = (su.B + pol::SPW - 1) / pol::SPW;
     hipLaunchKernelGGL((pol::k_policy_forward<false, true, pol::kEnvBoth>), dim3(grid), dim3(pol::NTHR), 0, (hipStream_t)stream,
-                       policy->weights, states, (int)B, nullptr, seed, offset, offset_dev, action_out, logp, value,
-                       nullptr, nullptr, pol::TrainIO{}, rio, *env,
+                       policy->weights, states, (int)su.B, nullptr, seed, offset, offset_dev, action_out, logp, value,
+                       nullptr, nullptr, pol::TrainIO{}, su.rio, *env,
                        pol::EnvOut{(int)auto_reset, obs_out, reward, done, info});
     return check_launch("k_rollout_step");
 }
@@ -1737,21 +1760,16 @@ extern "C" int uavhip_rollout_steps(const uavhip_policy* policy, const uavhip_en
                                     uint64_t offset_stride, const uint64_t* offset_dev, int8_t* actions, float* logp,
                                     float* value, int32_t auto_reset, double* reward, uint8_t* done, double* info,
                                     uavhip_stream_t stream) {
-    if (const int rc = validate_env(env, true)) return rc;
-    const int32_t B = env->E;
-    if (const int rc = check_policy("uavhip_rollout_steps", policy, obs, B)) return rc;
-    if (env->N > 64 || env->M > 64 || (env->flags & UAVHIP_ENV_OBS_F16) || !actions || !logp || !value || !reward ||
-        !done || n <= 0) {
-        set_error("uavhip_rollout_steps: N=%d, M=%d must be <= 64, observations f32, n=%d > 0 and "
-                  "actions/logp/value/reward/done non-NULL", env->N, env->M, n);
-        return UAVHIP_EINVAL;
-    }
-    pol::RowIO rio;
-    if (const int rc = ring_setup("uavhip_rollout_steps", "E", policy, obs, B, rowproj, step, fill, stream, &rio)) return rc;
-    const long long stride = (long long)B * pol::S * pol::IN;
-    return pol::launch_rollout_steps(policy->weights, obs, (int)B, seed, offset, offset_dev, actions, logp, value, rio,
-                                     *env, pol::EnvOut{(int)auto_reset, obs + stride, reward, done, info},
-                                     pol::StepSeq{(int)n, stride, offset_stride}, (hipStream_t)stream);
+    StepSetup su;
+    if (const int rc = step_setup(&su, "uavhip_rollout_steps", policy, env, obs, false, rowproj, step, fill, stream, true,
+                                  actions && logp && value && reward && done && n > 0,
+                                  ", n=%d > 0 and actions/logp/value/reward/done non-NULL", n))
+        return rc;
+    return pol::launch_rollout_steps(
+        pol::StepsArgs{policy->weights, obs, (int)su.B, seed, offset, offset_dev, actions, logp, value, su.rio, *env,
+                       pol::EnvOut{(int)auto_reset, obs + su.stride, reward, done, info},
+                       pol::StepSeq{(int)n, su.stride, offset_stride}},
+        (hipStream_t)stream);
 }
 
 // uavhip_rollout_steps without the critic (k_rollout_actor_steps); uavhip_value_steps supplies the values.
@@ -1760,22 +1778,16 @@ extern "C" int uavhip_rollout_actor_steps(const uavhip_policy* policy, const uav
                                           uint64_t offset, uint64_t offset_stride, const uint64_t* offset_dev,
                                           int8_t* actions, float* logp, int32_t auto_reset, double* reward,
                                           uint8_t* done, double* info, uavhip_stream_t stream) {
-    if (const int rc = validate_env(env, true)) return rc;
-    const int32_t B = env->E;
-    if (const int rc = check_policy("uavhip_rollout_actor_steps", policy, obs, B)) return rc;
-    if (env->N > 64 || env->M > 64 || (env->flags & UAVHIP_ENV_OBS_F16) || !actions || !logp || !reward || !done ||
-        n <= 0) {
-        set_error("uavhip_rollout_actor_steps: N=%d, M=%d must be <= 64, observations f32, n=%d > 0 and "
-                  "actions/logp/reward/done non-NULL", env->N, env->M, n);
-        return UAVHIP_EINVAL;
-    }
-    pol::RowIO rio;
-    if (const int rc = ring_setup("uavhip_rollout_actor_steps", "E", policy, obs, B, rowproj, step, fill, stream, &rio))
+    StepSetup su;
+    if (const int rc = step_setup(&su, "uavhip_rollout_actor_steps", policy, env, obs, false, rowproj, step, fill, stream,
+                                  true, actions && logp && reward && done && n > 0,
+                                  ", n=%d > 0 and actions/logp/reward/done non-NULL", n))
         return rc;
-    const long long stride = (long long)B * pol::S * pol::IN;
-    return pol::launch_rollout_actor_steps(policy->weights, obs, (int)B, seed, offset, offset_dev, actions, logp, rio,
-                                           *env, pol::EnvOut{(int)auto_reset, obs + stride, reward, done, info},
-                                           pol::StepSeq{(int)n, stride, offset_stride}, (hipStream_t)stream);
+    return pol::launch_rollout_actor_steps(
+        pol::StepsArgs{policy->weights, obs, (int)su.B, seed, offset, offset_dev, actions, logp, nullptr, su.rio, *env,
+                       pol::EnvOut{(int)auto_reset, obs + su.stride, reward, done, info},
+                       pol::StepSeq{(int)n, su.stride, offset_stride}},
+        (hipStream_t)stream);
 }
 
 // The values of the recorded windows obs[0 .. n - 1] (and of obs[n] when last_values is given) on the
@@ -1787,13 +1799,12 @@ extern "C" int uavhip_value_steps(const uavhip_policy* policy, const float* obs,
                                   int32_t step, int32_t fill, float* values, float* last_values, float* stash,
                                   uavhip_stream_t stream) {
     if (const int rc = check_policy("uavhip_value_steps", policy, obs, B)) return rc;
-    if (!rowproj || !values || !stash || n <= 0 || step < 0 || (int64_t)B * pol::S * pol::kRowFloats >= (int64_t)1 << 31) {
-        set_error("uavhip_value_steps: NULL rowproj / values / stash, n=%d <= 0, step=%d < 0 or B=%d above the ring's 32-bit "
-                  "offsets", n, step, B);
-        return UAVHIP_EINVAL;
-    }
-    const pol::RowIO rio{rowproj, (int)B, (int)step};
-    if (const int rc = ring_fill(policy, obs, rio, fill, stream)) return rc;
+    char also[64];
+    snprintf(also, sizeof also, " / values / stash, n=%d <= 0", n);
+    pol::RowIO rio;
+    if (const int rc = ring_setup("uavhip_value_steps", "B", policy, obs, B, rowproj, step, fill, stream, &rio, also,
+                                  values && stash && n > 0))
+        return rc;
     return pol::launch_value_steps(pol::ValueArgs{policy->weights, obs, (int)B, (int)n, (long long)B * pol::S * pol::IN,
                                                   rio, values, last_values, stash},
                                    (hipStream_t)stream);
@@ -1805,22 +1816,13 @@ extern "C" int uavhip_decode_steps(const uavhip_policy* policy, const uavhip_env
                                    uint64_t offset, uint64_t offset_stride, const uint64_t* offset_dev,
                                    int8_t* actions, int32_t* steps, uint8_t* finished, double* ep_return,
                                    uavhip_stream_t stream) {
-    if (const int rc = validate_env(env, true)) return rc;
-    const int32_t B = env->E;
-    if (const int rc = check_policy("uavhip_decode_steps", policy, obs2, B)) return rc;
-    if (env->N > 64 || env->M > 64 || (env->flags & UAVHIP_ENV_OBS_F16) || n_max <= 0 || greedy_stride < 0 || !steps ||
-        !finished) {
-        set_error("uavhip_decode_steps: N=%d, M=%d must be <= 64, observations f32, n_max=%d > 0, "
-                  "greedy_stride=%d >= 0 and steps/finished non-NULL", env->N, env->M, n_max, greedy_stride);
-        return UAVHIP_EINVAL;
-    }
-    const long long stride = (long long)B * pol::S * pol::IN;
-    pol::RowIO rio;
-    if (const int rc = ring_setup("uavhip_decode_steps", "E", policy, obs2 + (step & 1) * stride, B, rowproj, step, fill,
-                                  stream, &rio))
+    StepSetup su;
+    if (const int rc = step_setup(&su, "uavhip_decode_steps", policy, env, obs2, true, rowproj, step, fill, stream, true,
+                                  n_max > 0 && greedy_stride >= 0 && steps && finished,
+                                  ", n_max=%d > 0, greedy_stride=%d >= 0 and steps/finished non-NULL", n_max, greedy_stride))
         return rc;
-    return pol::launch_decode_steps(pol::DecodeArgs{policy->weights, obs2, (int)B, seed, offset, offset_dev, rio, *env,
-                                                    (int)n_max, (int)greedy_stride, stride, offset_stride, actions,
-                                                    steps, finished, ep_return},
+    return pol::launch_decode_steps(pol::DecodeArgs{policy->weights, obs2, (int)su.B, seed, offset, offset_dev, su.rio,
+                                                    *env, (int)n_max, (int)greedy_stride, su.stride, offset_stride,
+                                                    actions, steps, finished, ep_return},
                                     (hipStream_t)stream);
 }

@@ -19,11 +19,24 @@ struct StepSeq {
     long long obs_stride;  // floats from obs[t] to obs[t + 1] (E * 5 * 14)
     uint64_t off_stride;   // sampling counter advance per step
 };
+// All of the launch's arguments in one struct: the kernel's only parameter, so the kernarg
+// segment holds exactly this struct at offset 0.
+struct StepsArgs {
+    const float* P;
+    const float* states;
+    int B;
+    uint64_t seed, offset;
+    const uint64_t* offset_dev;
+    int8_t* action_out;
+    float *logp_out, *value_out;
+    RowIO rio;
+    uavhip_env env;
+    EnvOut eo;
+    StepSeq seq;
+};
 // k_rollout_steps is compiled in its own translation unit (rollout_steps.hip: the same forward headers
 // with UAVHIP_STEPS_TU + UAVHIP_TID_LAUNDER); uavhip_rollout_steps launches it through this.
-int launch_rollout_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
-                         const uint64_t* offset_dev, int8_t* actions, float* logp, float* value, const RowIO& rio,
-                         const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream);
+int launch_rollout_steps(const StepsArgs& sa, hipStream_t stream);
 // k_decode_steps' only parameter (uavhip_decode_steps; the same translation unit as k_rollout_steps)
 struct DecodeArgs {
     const float* P;
@@ -42,10 +55,8 @@ struct DecodeArgs {
     double* ep_return;     // [B] (nullable); between the steps the env step's reward
 };
 int launch_decode_steps(const DecodeArgs& da, hipStream_t stream);
-// k_rollout_actor_steps (uavhip_rollout_actor_steps): k_rollout_steps' arguments without the value
-int launch_rollout_actor_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
-                               const uint64_t* offset_dev, int8_t* actions, float* logp, const RowIO& rio,
-                               const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream);
+// k_rollout_actor_steps (uavhip_rollout_actor_steps): k_rollout_steps' arguments, value_out not read
+int launch_rollout_actor_steps(const StepsArgs& sa, hipStream_t stream);
 // k_value_steps' only parameter (uavhip_value_steps; the same translation unit as k_rollout_steps)
 struct ValueArgs {
     const float* P;
@@ -59,21 +70,6 @@ struct ValueArgs {
 };
 int launch_value_steps(const ValueArgs& va, hipStream_t stream);
 constexpr int kVG = S;  // k_value_steps: windows per group, one 16-token tile each
-// All of the launch's arguments in one struct: the kernel's only parameter, so the kernarg
-// segment holds exactly this struct at offset 0.
-struct StepsArgs {
-    const float* P;
-    const float* states;
-    int B;
-    uint64_t seed, offset;
-    const uint64_t* offset_dev;
-    int8_t* action_out;
-    float *logp_out, *value_out;
-    RowIO rio;
-    uavhip_env env;
-    EnvOut eo;
-    StepSeq seq;
-};
 
 }  // namespace pol
 }  // namespace uavhip

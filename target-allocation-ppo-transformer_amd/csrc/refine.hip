@@ -9,8 +9,6 @@
 // One wave per scene, four per workgroup (as k_select_best); the wave's view of its row -- registers,
 // id conversion, sweeps, scoring -- is RefineRow (refine_device.hpp), which k_search (search.hip)
 // runs too. The env and the scene are only read.
-#include <cstdio>
-
 #include "refine_device.hpp"
 
 namespace uavhip {
@@ -39,34 +37,10 @@ extern "C" int uavhip_refine_assignments(const uavhip_env* env, int32_t env_stri
                                          const int32_t* assignment_in, int32_t* assignment_out, double* J,
                                          int32_t* covered, int32_t* stats, uavhip_stream_t stream) {
     using namespace uavhip;
-    if (const int rc = validate_env(env, false)) {
-        char why[256];
-        snprintf(why, sizeof why, "%s", uavhip_last_error());
-        set_error("uavhip_refine_assignments: %s", why);
+    if (const int rc = check_rows("uavhip_refine_assignments", env, env_stride, S,
+                                  max_sweeps >= 0 && assignment_out && J && covered, "max_sweeps=%d >= 0", max_sweeps))
         return rc;
-    }
-    if (env_stride < 1 || S < 1 || (long long)(S - 1) * env_stride >= env->E || max_sweeps < 0 || !assignment_out ||
-        !J || !covered) {
-        set_error("uavhip_refine_assignments: need env_stride=%d >= 1, S=%d >= 1, (S - 1) * env_stride < E=%d, "
-                  "max_sweeps=%d >= 0 and assignment_out/J/covered non-NULL",
-                  env_stride, S, env->E, max_sweeps);
-        return UAVHIP_EINVAL;
-    }
-    const dim3 grid((S + kRefineWaves - 1) / kRefineWaves), block(64 * kRefineWaves);
-    const hipStream_t st = (hipStream_t)stream;
-#define UAVHIP_REFINE(TPL, NCAP)                                                                                \
-    hipLaunchKernelGGL((k_refine<TPL, NCAP>), grid, block, 0, st, *env, (int)env_stride, (int)S, (int)max_sweeps, \
-                       assignment_in, assignment_out, J, covered, stats)
-    if (env->M > kWave)
-        UAVHIP_REFINE(2, 0);
-    else if (env->N <= 8)
-        UAVHIP_REFINE(1, 8);
-    else if (env->N <= 16)
-        UAVHIP_REFINE(1, 16);
-    else if (env->N <= 32)
-        UAVHIP_REFINE(1, 32);
-    else
-        UAVHIP_REFINE(1, 0);
-#undef UAVHIP_REFINE
+    UAVHIP_ROWS_LAUNCH(env, S, (k_refine<TPL, NCAP>), stream, *env, (int)env_stride, (int)S, (int)max_sweeps, assignment_in,
+                       assignment_out, J, covered, stats);
     return check_launch("k_refine");
 }

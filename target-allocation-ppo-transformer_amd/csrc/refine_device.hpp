@@ -13,6 +13,9 @@
 //  * NCAP == 0 (N > 32 or M > 64): only the assigned UAVs contribute, so the rebuild loads the one
 //    element p_dmg[w][a[w]] per assigned w (L1 / L2 hits after the first sweep) in lane a[w].
 #pragma once
+#include <cstdarg>
+#include <cstdio>
+
 #include "common.hpp"
 
 namespace uavhip {
@@ -226,4 +229,41 @@ struct RefineRow {
     }
 };
 
+// ------------------------------------------------------------------ host: what the two entry points share
+// The env and the rows of entry point `fn` (row s < S on the scene of env s * env_stride), and the rest
+// of its arguments: `rest_ok`, with `caps` (a format and its values) naming the caps in the message.
+inline int check_rows(const char* fn, const uavhip_env* env, int32_t env_stride, int32_t S, bool rest_ok,
+                      const char* caps, ...) {
+    if (const int rc = validate_env_for(fn, env, false)) return rc;
+    if (env_stride >= 1 && S >= 1 && (long long)(S - 1) * env_stride < env->E && rest_ok) return UAVHIP_OK;
+    char c[96];
+    va_list ap;
+    va_start(ap, caps);
+    vsnprintf(c, sizeof c, caps, ap);
+    va_end(ap);
+    set_error("%s: need env_stride=%d >= 1, S=%d >= 1, (S - 1) * env_stride < E=%d, %s and assignment_out/J/covered "
+              "non-NULL", fn, env_stride, S, env->E, c);
+    return UAVHIP_EINVAL;
+}
+
 }  // namespace uavhip
+
+// UAVHIP_WITH_ROW_SHAPE runs its statement with RefineRow's TPL and NCAP bound to the constants of the
+// env's shape: two targets per lane for M > 64, else the register column of the smallest cap that holds
+// N. UAVHIP_ROWS_LAUNCH launches `kern` (an expression in them, in parentheses) over S rows, one wave each.
+#define UAVHIP_ROWS_CASE(T, C, ...)      \
+    {                                    \
+        constexpr int TPL = T, NCAP = C; \
+        __VA_ARGS__;                     \
+    }
+#define UAVHIP_WITH_ROW_SHAPE(env, ...)                                          \
+    do {                                                                         \
+        if ((env)->M > ::uavhip::kWave) UAVHIP_ROWS_CASE(2, 0, __VA_ARGS__)      \
+        else if ((env)->N <= 8) UAVHIP_ROWS_CASE(1, 8, __VA_ARGS__)              \
+        else if ((env)->N <= 16) UAVHIP_ROWS_CASE(1, 16, __VA_ARGS__)            \
+        else if ((env)->N <= 32) UAVHIP_ROWS_CASE(1, 32, __VA_ARGS__)            \
+        else UAVHIP_ROWS_CASE(1, 0, __VA_ARGS__)                                 \
+    } while (0)
+#define UAVHIP_ROWS_LAUNCH(env, S, kern, stream, ...)                                                              \
+    UAVHIP_WITH_ROW_SHAPE(env, hipLaunchKernelGGL(kern, dim3(((S) + ::uavhip::kRefineWaves - 1) / ::uavhip::kRefineWaves), \
+                                                  dim3(64 * ::uavhip::kRefineWaves), 0, (hipStream_t)(stream), __VA_ARGS__))

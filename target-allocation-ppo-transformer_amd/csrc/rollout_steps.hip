@@ -26,7 +26,35 @@ namespace uavhip { namespace pol { __device__ unsigned long long g_strace[256 * 
 namespace uavhip {
 namespace pol {
 
-template <int ENVP>  // kEnvGrp / kEnvWave (launch_rollout_steps picks)
+// A multi-step kernel's view of its arguments (struct Args, its only parameter) for one step: `a`, read
+// through a kernarg pointer laundered here, so the loads sit where the body uses them instead of being
+// hoisted out of the loop and kept live (spilled) across the whole body; pointers loaded from the
+// constant address space are still known global. With it `bx` = blockIdx.x and `tid`, the forward
+// helpers' lane index (TID_F), both opaque per step; the mask restores threadIdx.x's range, which the
+// launder hides from the compiler. A macro: the text of the block, nothing the compiler could treat otherwise.
+#define UAVHIP_KARGS(Args)                                       \
+    typedef const __attribute__((address_space(4))) Args* kargs; \
+    kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();    \
+    int bx = blockIdx.x;                                         \
+    unsigned tid = threadIdx.x;                                  \
+    asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));            \
+    tid &= NTHR - 1;                                             \
+    const Args& a = *(const Args*)ka
+
+// Launch the instantiation of a fused step kernel for the env path of args.env over args.B envs: two
+// envs per wave wherever every wave's envs come in pairs (policy_block's env_grp for all of them), the
+// grouped path alone; else the one-env-per-wave path alone (bitwise the same steps).
+template <auto KGrp, auto KWave, class Args>
+int launch_env_path(const Args& args, const char* name, hipStream_t stream) {
+    const dim3 grid((args.B + SPW - 1) / SPW), block(NTHR);
+    if (args.env.N <= envgrp::L && args.env.M <= envgrp::L && args.B % 2 == 0)
+        hipLaunchKernelGGL(KGrp, grid, block, 0, stream, args);
+    else
+        hipLaunchKernelGGL(KWave, grid, block, 0, stream, args);
+    return check_launch(name);
+}
+
+template <int ENVP>  // kEnvGrp / kEnvWave (launch_env_path picks)
 __global__ __launch_bounds__(NTHR) void k_rollout_steps(const StepsArgs args) {
     __shared__ __attribute__((aligned(16))) Smem sm;
     if (threadIdx.x >= NTHR / 2) __builtin_amdgcn_s_setprio(1);
@@ -34,16 +62,7 @@ __global__ __launch_bounds__(NTHR) void k_rollout_steps(const StepsArgs args) {
     load_rtab(TID_K sm, args.P);  // the weights are the launch's: once
     for (int t = 0; t < args.seq.n; ++t) {
         __syncthreads();  // g_tid_zero; the previous step's LDS scratch and global stores
-        // Every argument is read through a kernarg pointer laundered per step, so the loads sit where
-        // the body uses them instead of being hoisted out of the loop and kept live (spilled) across
-        // the whole body; pointers loaded from the constant address space are still known global.
-        typedef const __attribute__((address_space(4))) StepsArgs* kargs;
-        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-        int bx = blockIdx.x;
-        unsigned tid = threadIdx.x;  // the forward helpers' lane index, opaque per step (TID_F)
-        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-        tid &= NTHR - 1;  // threadIdx.x's range, which the launder hides from the compiler
-        const StepsArgs& a = *(const StepsArgs*)ka;
+        UAVHIP_KARGS(StepsArgs);
         const size_t o = (size_t)t * a.B;
         const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
         const EnvOut e{a.eo.auto_reset, a.eo.obs + t * a.seq.obs_stride, a.eo.rew + o, a.eo.done + o,
@@ -55,22 +74,11 @@ __global__ __launch_bounds__(NTHR) void k_rollout_steps(const StepsArgs args) {
 }
 #ifdef UAVHIP_POLICY_TRACE
 extern "C" int uavhip_steps_trace(unsigned long long* out, int n) {  // the last step's k_rollout_steps stamps
-    const int total = 256 * 2 * kTraceSlots;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ptrace), sizeof(unsigned long long) * (n < total ? n : total), 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    return copy_trace(g_ptrace, 256 * 2 * kTraceSlots, out, n);
 }
 #endif
-int launch_rollout_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
-                         const uint64_t* offset_dev, int8_t* actions, float* logp, float* value, const RowIO& rio,
-                         const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream) {
-    // two envs per wave wherever every wave's envs come in pairs (policy_block's env_grp for all of
-    // them): the grouped path alone; else the one-env-per-wave path alone (bitwise the same steps)
-    const StepsArgs sa{P, obs, B, seed, offset, offset_dev, actions, logp, value, rio, env, eo, seq};
-    if (env.N <= envgrp::L && env.M <= envgrp::L && B % 2 == 0)
-        hipLaunchKernelGGL(k_rollout_steps<kEnvGrp>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
-    else
-        hipLaunchKernelGGL(k_rollout_steps<kEnvWave>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
-    return check_launch("k_rollout_steps");
+int launch_rollout_steps(const StepsArgs& sa, hipStream_t stream) {
+    return launch_env_path<k_rollout_steps<kEnvGrp>, k_rollout_steps<kEnvWave>>(sa, "k_rollout_steps", stream);
 }
 
 // Decode (uavhip_decode_steps): k_rollout_steps' loop with the actor-only block (policy_block AONLY)
@@ -126,13 +134,7 @@ __global__ __launch_bounds__(NTHR) void k_decode_steps(const DecodeArgs args) {
     int t = 0;
     for (;;) {
         __syncthreads();  // s_all; g_tid_zero; the previous step's LDS scratch and global stores
-        typedef const __attribute__((address_space(4))) DecodeArgs* kargs;
-        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-        int bx = blockIdx.x;
-        unsigned tid = threadIdx.x;
-        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-        tid &= NTHR - 1;
-        const DecodeArgs& a = *(const DecodeArgs*)ka;
+        UAVHIP_KARGS(DecodeArgs);
         // workgroup-uniform: every wave reads the flag wave 0 wrote before the barrier
         if (__builtin_amdgcn_readfirstlane(s_all) || t >= a.n_max) break;
         const int slot = (a.rio.g + t) & 1;
@@ -148,13 +150,7 @@ __global__ __launch_bounds__(NTHR) void k_decode_steps(const DecodeArgs args) {
     }
     // the envs' totals; the trace rows the workgroup did not run (the arguments through a kernarg
     // pointer of their own again: loaded here, not kept from the prologue across the loop)
-    typedef const __attribute__((address_space(4))) DecodeArgs* kargs;
-    kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-    int bx = blockIdx.x;
-    unsigned tid = threadIdx.x;
-    asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-    tid &= NTHR - 1;
-    const DecodeArgs& a = *(const DecodeArgs*)ka;
+    UAVHIP_KARGS(DecodeArgs);
     const int e0 = bx * SPW;
     if (tid < SPW && e0 + (int)tid < a.B) {
         const int p = tid, e = e0 + p;
@@ -170,12 +166,7 @@ __global__ __launch_bounds__(NTHR) void k_decode_steps(const DecodeArgs args) {
     }
 }
 int launch_decode_steps(const DecodeArgs& da, hipStream_t stream) {
-    // one env path per instantiation, chosen as launch_rollout_steps chooses
-    if (da.env.N <= envgrp::L && da.env.M <= envgrp::L && da.B % 2 == 0)
-        hipLaunchKernelGGL(k_decode_steps<kEnvGrp>, dim3((da.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, da);
-    else
-        hipLaunchKernelGGL(k_decode_steps<kEnvWave>, dim3((da.B + SPW - 1) / SPW), dim3(NTHR), 0, stream, da);
-    return check_launch("k_decode_steps");
+    return launch_env_path<k_decode_steps<kEnvGrp>, k_decode_steps<kEnvWave>>(da, "k_decode_steps", stream);
 }
 
 // Rollout with the critic taken off the step chain (uavhip_rollout_actor_steps + uavhip_value_steps).
@@ -194,13 +185,7 @@ __global__ __launch_bounds__(NTHR) void k_rollout_actor_steps(const StepsArgs ar
     load_rtab(TID_K sm, args.P);
     for (int t = 0; t < args.seq.n; ++t) {
         __syncthreads();  // g_tid_zero; the previous step's LDS scratch and global stores
-        typedef const __attribute__((address_space(4))) StepsArgs* kargs;
-        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-        int bx = blockIdx.x;
-        unsigned tid = threadIdx.x;
-        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-        tid &= NTHR - 1;
-        const StepsArgs& a = *(const StepsArgs*)ka;
+        UAVHIP_KARGS(StepsArgs);
         const size_t o = (size_t)t * a.B;
         const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
         const EnvOut e{a.eo.auto_reset, a.eo.obs + t * a.seq.obs_stride, a.eo.rew + o, a.eo.done + o,
@@ -211,16 +196,9 @@ __global__ __launch_bounds__(NTHR) void k_rollout_actor_steps(const StepsArgs ar
                                                      TrainIO{}, r, a.env, e, bx, 0);
     }
 }
-int launch_rollout_actor_steps(const float* P, float* obs, int B, uint64_t seed, uint64_t offset,
-                               const uint64_t* offset_dev, int8_t* actions, float* logp, const RowIO& rio,
-                               const uavhip_env& env, const EnvOut& eo, const StepSeq& seq, hipStream_t stream) {
-    // one env path per instantiation, chosen as launch_rollout_steps chooses
-    const StepsArgs sa{P, obs, B, seed, offset, offset_dev, actions, logp, nullptr, rio, env, eo, seq};
-    if (env.N <= envgrp::L && env.M <= envgrp::L && B % 2 == 0)
-        hipLaunchKernelGGL(k_rollout_actor_steps<kEnvGrp>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
-    else
-        hipLaunchKernelGGL(k_rollout_actor_steps<kEnvWave>, dim3((B + SPW - 1) / SPW), dim3(NTHR), 0, stream, sa);
-    return check_launch("k_rollout_actor_steps");
+int launch_rollout_actor_steps(const StepsArgs& sa, hipStream_t stream) {  // sa.value_out is not read
+    return launch_env_path<k_rollout_actor_steps<kEnvGrp>, k_rollout_actor_steps<kEnvWave>>(sa, "k_rollout_actor_steps",
+                                                                                          stream);
 }
 
 // k_value_steps: the windows in groups of kVG consecutive steps (the last group may be shorter). Per
@@ -281,26 +259,14 @@ __global__ __launch_bounds__(NTHR) void k_value_steps(const ValueArgs args) {
     for (int t0 = 0; t0 < nt; t0 += kVG) {
         for (int w = 0; w < kVG && t0 + w < nt; ++w) {
             __syncthreads();  // g_tid_zero; the previous window's LDS reads and ring-row stores
-            typedef const __attribute__((address_space(4))) ValueArgs* kargs;
-            kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-            int bx = blockIdx.x;
-            unsigned tid = threadIdx.x;
-            asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-            tid &= NTHR - 1;
-            const ValueArgs& a = *(const ValueArgs*)ka;
+            UAVHIP_KARGS(ValueArgs);
             const int t = t0 + w;
             const RowIO r{a.rio.rp, a.rio.B, a.rio.g + t};
             value_front(tid, sm, a.P, a.obs + t * a.obs_stride, a.B, r, bx * SPW,
                         reinterpret_cast<f32x4*>(a.stash) + ((size_t)bx * kVG + w) * kStashVec);
         }
         __syncthreads();  // the stash stores (read back by other lanes); sm.ctx is rewritten
-        typedef const __attribute__((address_space(4))) ValueArgs* kargs;
-        kargs ka = (kargs)__builtin_amdgcn_kernarg_segment_ptr();
-        int bx = blockIdx.x;
-        unsigned tid = threadIdx.x;
-        asm volatile("" : "+s"(ka), "+s"(bx), "+v"(tid));
-        tid &= NTHR - 1;
-        const ValueArgs& a = *(const ValueArgs*)ka;
+        UAVHIP_KARGS(ValueArgs);
         const int gw = min(kVG, nt - t0), b0 = bx * SPW;
         PTR(5);
         // tile w <- window w: the planes to sm.ctx (every load issued before the first LDS store;

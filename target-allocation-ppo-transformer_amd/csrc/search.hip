@@ -17,8 +17,6 @@
 // loads, p_dmg[j][a[i]] and p_dmg[i][a[j]] -- about N gathered loads per UAV and scan. The lane keeps
 // its best over i (strict >: the lowest i), a six-step butterfly on (d, i, j) the lowest (i, j)
 // among equal d. No LDS, no atomics, nothing shared between waves; the env and the scene are only read.
-#include <cstdio>
-
 #include "refine_device.hpp"
 
 namespace uavhip {
@@ -134,34 +132,11 @@ extern "C" int uavhip_search_assignments(const uavhip_env* env, int32_t env_stri
                                          int32_t max_sweeps, const int32_t* assignment_in, int32_t* assignment_out,
                                          double* J, int32_t* covered, int32_t* stats, uavhip_stream_t stream) {
     using namespace uavhip;
-    if (const int rc = validate_env(env, false)) {
-        char why[256];
-        snprintf(why, sizeof why, "%s", uavhip_last_error());
-        set_error("uavhip_search_assignments: %s", why);
+    if (const int rc = check_rows("uavhip_search_assignments", env, env_stride, S,
+                                  max_exchanges >= 0 && max_sweeps >= 0 && assignment_out && J && covered,
+                                  "max_exchanges=%d >= 0, max_sweeps=%d >= 0", max_exchanges, max_sweeps))
         return rc;
-    }
-    if (env_stride < 1 || S < 1 || (long long)(S - 1) * env_stride >= env->E || max_exchanges < 0 || max_sweeps < 0 ||
-        !assignment_out || !J || !covered) {
-        set_error("uavhip_search_assignments: need env_stride=%d >= 1, S=%d >= 1, (S - 1) * env_stride < E=%d, "
-                  "max_exchanges=%d >= 0, max_sweeps=%d >= 0 and assignment_out/J/covered non-NULL",
-                  env_stride, S, env->E, max_exchanges, max_sweeps);
-        return UAVHIP_EINVAL;
-    }
-    const dim3 grid((S + kRefineWaves - 1) / kRefineWaves), block(64 * kRefineWaves);
-    const hipStream_t st = (hipStream_t)stream;
-#define UAVHIP_SEARCH(TPL, NR)                                                                          \
-    hipLaunchKernelGGL((k_search<TPL, NR>), grid, block, 0, st, *env, (int)env_stride, (int)S, (int)max_exchanges, \
-                       (int)max_sweeps, assignment_in, assignment_out, J, covered, stats)
-    if (env->M > kWave)
-        UAVHIP_SEARCH(2, 0);
-    else if (env->N <= 8)
-        UAVHIP_SEARCH(1, 8);
-    else if (env->N <= 16)
-        UAVHIP_SEARCH(1, 16);
-    else if (env->N <= 32)
-        UAVHIP_SEARCH(1, 32);
-    else
-        UAVHIP_SEARCH(1, 0);
-#undef UAVHIP_SEARCH
+    UAVHIP_ROWS_LAUNCH(env, S, (k_search<TPL, NCAP>), stream, *env, (int)env_stride, (int)S, (int)max_exchanges,
+                       (int)max_sweeps, assignment_in, assignment_out, J, covered, stats);
     return check_launch("k_search");
 }

@@ -13,8 +13,6 @@
 // launch, pair probabilities read from global memory (no LDS table; the only LDS is push_obs' 16-float
 // row scratch per wave). Episodes end anywhere between N and N * M steps: a finished env is held
 // (UAVHIP_STEP_HOLD), its rows are a zero window, action -1, reward 0, done 1.
-#include <cstdio>
-
 #include "env_device.hpp"
 
 #pragma clang fp contract(off)
@@ -117,27 +115,13 @@ extern "C" int uavhip_teacher_steps(const uavhip_env* env, const int32_t* assign
                                     int8_t* actions, double* reward, uint8_t* done, double* info, int32_t* steps,
                                     uint8_t* finished, double* ep_return, int32_t* stats, uavhip_stream_t stream) {
     using namespace uavhip;
-    if (const int rc = validate_env(env, true)) {
-        char why[256];
-        snprintf(why, sizeof why, "%s", uavhip_last_error());
-        set_error("uavhip_teacher_steps: %s", why);
-        return rc;
-    }
+    if (const int rc = validate_env_for("uavhip_teacher_steps", env, true)) return rc;
     if (n_max < 1 || !assignment || !steps || !finished) {
         set_error("uavhip_teacher_steps: need n_max=%d >= 1 and assignment/steps/finished non-NULL", n_max);
         return UAVHIP_EINVAL;
     }
-    if (env->flags & UAVHIP_ENV_OBS_F16) {
-        set_error("uavhip_teacher_steps: f32 observations only (the env has UAVHIP_ENV_OBS_F16 set)");
-        return UAVHIP_EINVAL;
-    }
-    const dim3 grid((env->E + kWavesPerBlock - 1) / kWavesPerBlock), block(kBlock);
-    const hipStream_t st = (hipStream_t)stream;
-    if (env->M <= kWave)
-        hipLaunchKernelGGL(k_teacher_steps<1>, grid, block, 0, st, *env, assignment, (int)n_max, obs, actions, reward,
-                           done, info, steps, finished, ep_return, stats);
-    else
-        hipLaunchKernelGGL(k_teacher_steps<2>, grid, block, 0, st, *env, assignment, (int)n_max, obs, actions, reward,
-                           done, info, steps, finished, ep_return, stats);
+    if (const int rc = require_f32_obs("uavhip_teacher_steps", env)) return rc;
+    UAVHIP_WAVE_LAUNCH(env, k_teacher_steps<TPL>, 0, stream, *env, assignment, (int)n_max, obs, actions, reward, done, info,
+                       steps, finished, ep_return, stats);
     return check_launch("k_teacher_steps");
 }

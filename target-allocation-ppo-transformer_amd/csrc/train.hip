@@ -575,9 +575,7 @@ using namespace uavhip::tr;
 
 #ifdef UAVHIP_POLICY_TRACE
 extern "C" int uavhip_wgrad_trace(unsigned long long* out, int n) {  // k_wgrad stamps (TRACE build)
-    const int total = kWgGrid * 16;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wtrace), sizeof(unsigned long long) * (n < total ? n : total), 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    return copy_trace(g_wtrace, kWgGrid * 16, out, n);
 }
 #endif
 

@@ -206,6 +206,35 @@ def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _same_device(t, device):
+    return t.device.type == device.type and (device.index is None or t.device.index == device.index)
+
+
+def check_out(t, name, dtype, lead, device, tail=()):
+    """A caller-provided kernel buffer (read or written through a raw pointer): right device and
+    dtype, contiguous, exactly prod(lead + tail) elements -- anything else would be an out-of-bounds
+    or misread device access the C side cannot detect. None passes (NULL = not wanted)."""
+    if t is None:
+        return
+    n = 1
+    for d in tuple(lead) + tuple(tail):
+        n *= int(d)
+    if not isinstance(t, torch.Tensor) or not _same_device(t, device) or t.dtype != dtype or \
+            not t.is_contiguous() or t.numel() != n:
+        got = (f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous={t.is_contiguous()}"
+               if isinstance(t, torch.Tensor) else type(t).__name__)
+        raise ValueError(f"{name}: need a contiguous {dtype} tensor of {n} elements on {device} (got {got})")
+
+
+def out_buf(given, name, dtype, lead, device, tail=(), zero=False):
+    """A kernel's output buffer [*lead, *tail]: `given` itself once check_out passes it, else a fresh
+    tensor (zeroed where the kernel adds to it)."""
+    if given is not None:
+        check_out(given, name, dtype, lead, device, tail)
+        return given
+    return (torch.zeros if zero else torch.empty)(*lead, *tail, dtype=dtype, device=device)
+
+
 def stream_handle(stream=None):
     import torch
     s = torch.cuda.current_stream() if stream is None else stream

@@ -20,9 +20,8 @@ import torch.nn as nn
 from torch.distributions import Categorical
 
 from . import _lib
-from ._lib import LIB, check, ptr, stream_handle
+from ._lib import LIB, check, check_out, out_buf, ptr, stream_handle
 from .config import cfg
-from .vec_env import check_out
 
 
 def _ortho(layer, std=float(np.sqrt(2)), bias=0.0):
@@ -51,6 +50,28 @@ class _Trunk(nn.Module):
         pad[:, -1] = False                       # ... except the current step (transformer_net.py:52-54)
         h = self.embedding(x) + self.pos_embedding[:, :x.size(1), :]
         return self.transformer(h, src_key_padding_mask=pad)
+
+
+def _check_ring(rowproj, B, what):
+    """The window-row ring of a rows forward over B windows (`what`: the caller's name for B): a
+    contiguous float32 tensor of at least rowproj_buffer(B)'s elements, as the kernels index it."""
+    if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(B) or rowproj.dtype != torch.float32 or \
+            not rowproj.is_contiguous():
+        raise ValueError(f"rowproj: need a contiguous float32 rowproj_buffer({what})")
+
+
+def _steps_of(t, name, kind):
+    """n of a per-step [n][E] buffer (`kind`: its dtype and shape in words)."""
+    n = t.shape[0] if t.dim() == 2 else -1
+    if n <= 0:
+        raise ValueError(f"{name}: need {kind} buffer with n > 0")
+    return n
+
+
+def _check_outs(lead, dev, *bufs):
+    """check_out for every (tensor, name, dtype[, tail]) of `bufs`, all [*lead, *tail] on dev."""
+    for t, name, dtype, *tail in bufs:
+        check_out(t, name, dtype, lead, dev, *tail)
 
 
 _INSTANCES = itertools.count()
@@ -141,6 +162,11 @@ class TransformerActorCritic(nn.Module):
         self._desc = d
         return self._packed
 
+    def _ensure_packed(self):
+        """The wrappers of the fused kernels need packed weights; they do not repack current ones."""
+        if self._packed is None:
+            self.packed_weights()
+
     def fused_forward(self, states, actions=None, action_out=None, logp=None, value=None, entropy=None,
                       logits=None, seed=None, offset=None, offset_dev=None, check_weights=True, rowproj=None,
                       step=0, fill=True):
@@ -161,23 +187,19 @@ class TransformerActorCritic(nn.Module):
         if check_weights or self._packed is None:
             self.packed_weights()
         dev = states.device
-        action_out = torch.empty(B, dtype=torch.int8, device=dev) if action_out is None else action_out
-        logp = torch.empty(B, dtype=torch.float32, device=dev) if logp is None else logp
-        value = torch.empty(B, dtype=torch.float32, device=dev) if value is None else value
+        action_out = out_buf(action_out, "action_out", torch.int8, (B,), dev)
+        logp = out_buf(logp, "logp", torch.float32, (B,), dev)
+        value = out_buf(value, "value", torch.float32, (B,), dev)
         if actions is not None:
             actions = actions.to(device=dev, dtype=torch.int8).contiguous()
-            check_out(actions, "actions", torch.int8, (B,), dev)
-        for t, name, dt, tail in ((action_out, "action_out", torch.int8, ()), (logp, "logp", torch.float32, ()),
-                                  (value, "value", torch.float32, ()), (entropy, "entropy", torch.float32, ()),
-                                  (logits, "logits", torch.float32, (2,))):
-            check_out(t, name, dt, (B,), dev, tail)
+        _check_outs((B,), dev, (actions, "actions", torch.int8), (entropy, "entropy", torch.float32),
+                    (logits, "logits", torch.float32, (2,)))
         if offset is None:
             offset = self._sample_offset
             self._sample_offset += B
         seed = self.sample_seed if seed is None else seed
         if rowproj is not None:
-            if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(B) or rowproj.dtype != torch.float32:
-                raise ValueError("rowproj: need a float32 buffer of rowproj_buffer(B) elements")
+            _check_ring(rowproj, B, "B")
             check(LIB.uavhip_policy_forward_rows(self._desc, ptr(states), B, ptr(rowproj), int(step), int(bool(fill)),
                                                  ptr(actions), ctypes.c_uint64(seed), ctypes.c_uint64(offset),
                                                  ptr(offset_dev), ptr(action_out), ptr(logp), ptr(value),
@@ -195,13 +217,11 @@ class TransformerActorCritic(nn.Module):
         bitwise, without the actor trunk and sampling. The actor's ring row of this step is not
         written, so the next call on the sequence must fill (RolloutEngine refills every iteration).
         The weights must be packed (packed_weights())."""
-        if self._packed is None:
-            self.packed_weights()
+        self._ensure_packed()
         B = states.shape[0]
         check_out(states, "states", torch.float32, (B,), states.device, (cfg.SEQ_LEN, cfg.STATE_DIM))
         check_out(value, "value", torch.float32, (B,), states.device)
-        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(B) or rowproj.dtype != torch.float32:
-            raise ValueError("rowproj: need a float32 buffer of rowproj_buffer(B) elements")
+        _check_ring(rowproj, B, "B")
         check(LIB.uavhip_policy_value_rows(self._desc, ptr(states), B, ptr(rowproj), int(step), int(bool(fill)),
                                            ptr(value), stream_handle()), "uavhip_policy_value_rows")
         return value
@@ -211,19 +231,14 @@ class TransformerActorCritic(nn.Module):
         """uavhip_rollout_step: the window-row forward + sampling over env's E windows `states`
         and the env step of the sampled actions in one launch (VecUAVEnv `env`, N, M <= 64).
         The weights must be packed (packed_weights())."""
-        if self._packed is None:
-            self.packed_weights()
+        self._ensure_packed()
         E, dev = env.E, env.device
         env._check_obs(obs_out)
         check_out(states, "states", torch.float32, (E,), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
-        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or rowproj.dtype != torch.float32 or \
-                not rowproj.is_contiguous():
-            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
-        for t, name, dt, tail in ((action_out, "action_out", torch.int8, ()), (logp, "logp", torch.float32, ()),
-                                  (value, "value", torch.float32, ()), (reward_out, "reward_out", torch.float64, ()),
-                                  (done_out, "done_out", torch.uint8, ()),
-                                  (info_out, "info_out", torch.float64, (_lib.INFO_COUNT,))):
-            check_out(t, name, dt, (E,), dev, tail)
+        _check_ring(rowproj, E, "E")
+        _check_outs((E,), dev, (action_out, "action_out", torch.int8), (logp, "logp", torch.float32),
+                    (value, "value", torch.float32), (reward_out, "reward_out", torch.float64),
+                    (done_out, "done_out", torch.uint8), (info_out, "info_out", torch.float64, (_lib.INFO_COUNT,)))
         seed = self.sample_seed if seed is None else seed
         check(LIB.uavhip_rollout_step(self._desc, env.desc, ptr(states), ptr(rowproj), int(step), int(bool(fill)),
                                       ctypes.c_uint64(seed), ctypes.c_uint64(offset), ptr(offset_dev),
@@ -237,21 +252,14 @@ class TransformerActorCritic(nn.Module):
         obs [n + 1][E][5][14] f32 (obs[0] = the current windows; obs[t + 1] receives step t's next
         windows), actions / logp / value / rewards / dones [n][E], info [n][E][INFO_COUNT] or None;
         step t samples with counters offset + t * offset_stride + b (+ *offset_dev)."""
-        if self._packed is None:
-            self.packed_weights()
+        self._ensure_packed()
         E, dev = env.E, env.device
-        n = actions.shape[0] if actions.dim() == 2 else -1
-        if n <= 0:
-            raise ValueError("actions: need an int8 [n][E] buffer with n > 0")
+        n = _steps_of(actions, "actions", "an int8 [n][E]")
         check_out(obs, "obs", torch.float32, (n + 1, E), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
-        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or rowproj.dtype != torch.float32 or \
-                not rowproj.is_contiguous():
-            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
-        for t, name, dt, tail in ((actions, "actions", torch.int8, ()), (logp, "logp", torch.float32, ()),
-                                  (value, "value", torch.float32, ()), (rewards, "rewards", torch.float64, ()),
-                                  (dones, "dones", torch.uint8, ()),
-                                  (info, "info", torch.float64, (_lib.INFO_COUNT,))):
-            check_out(t, name, dt, (n, E), dev, tail)
+        _check_ring(rowproj, E, "E")
+        _check_outs((n, E), dev, (actions, "actions", torch.int8), (logp, "logp", torch.float32),
+                    (value, "value", torch.float32), (rewards, "rewards", torch.float64), (dones, "dones", torch.uint8),
+                    (info, "info", torch.float64, (_lib.INFO_COUNT,)))
         seed = self.sample_seed if seed is None else seed
         check(LIB.uavhip_rollout_steps(self._desc, env.desc, ptr(obs), ptr(rowproj), int(step), int(n),
                                        int(bool(fill)), ctypes.c_uint64(seed), ctypes.c_uint64(offset),
@@ -264,20 +272,14 @@ class TransformerActorCritic(nn.Module):
         """uavhip_rollout_actor_steps: rollout_steps() without the critic -- the same windows, actions,
         logp, rewards, dones, info, env state and actor ring rows, bitwise, and no value (value_steps()
         computes the values from the recorded windows afterwards)."""
-        if self._packed is None:
-            self.packed_weights()
+        self._ensure_packed()
         E, dev = env.E, env.device
-        n = actions.shape[0] if actions.dim() == 2 else -1
-        if n <= 0:
-            raise ValueError("actions: need an int8 [n][E] buffer with n > 0")
+        n = _steps_of(actions, "actions", "an int8 [n][E]")
         check_out(obs, "obs", torch.float32, (n + 1, E), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
-        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or rowproj.dtype != torch.float32 or \
-                not rowproj.is_contiguous():
-            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
-        for t, name, dt, tail in ((actions, "actions", torch.int8, ()), (logp, "logp", torch.float32, ()),
-                                  (rewards, "rewards", torch.float64, ()), (dones, "dones", torch.uint8, ()),
-                                  (info, "info", torch.float64, (_lib.INFO_COUNT,))):
-            check_out(t, name, dt, (n, E), dev, tail)
+        _check_ring(rowproj, E, "E")
+        _check_outs((n, E), dev, (actions, "actions", torch.int8), (logp, "logp", torch.float32),
+                    (rewards, "rewards", torch.float64), (dones, "dones", torch.uint8),
+                    (info, "info", torch.float64, (_lib.INFO_COUNT,)))
         seed = self.sample_seed if seed is None else seed
         check(LIB.uavhip_rollout_actor_steps(self._desc, env.desc, ptr(obs), ptr(rowproj), int(step), int(n),
                                              int(bool(fill)), ctypes.c_uint64(seed), ctypes.c_uint64(offset),
@@ -291,18 +293,13 @@ class TransformerActorCritic(nn.Module):
         V(obs[n]). Bitwise the values rollout_steps() / value_rows() write. step: the ring step of
         obs[0]; fill=True rebuilds the ring rows from obs[0] first. The kernel's scratch
         (uavhip_value_steps_stash_floats(B) floats) is allocated on first use and kept per (B, device)."""
-        if self._packed is None:
-            self.packed_weights()
-        n = values.shape[0] if values.dim() == 2 else -1
-        if n <= 0:
-            raise ValueError("values: need a float32 [n][B] buffer with n > 0")
+        self._ensure_packed()
+        n = _steps_of(values, "values", "a float32 [n][B]")
         B, dev = values.shape[1], obs.device
         check_out(obs, "obs", torch.float32, (n + 1, B), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
         check_out(values, "values", torch.float32, (n, B), dev)
         check_out(last_values, "last_values", torch.float32, (B,), dev)
-        if rowproj.numel() < LIB.uavhip_policy_rowproj_floats(B) or rowproj.dtype != torch.float32 or \
-                not rowproj.is_contiguous():
-            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(B)")
+        _check_ring(rowproj, B, "B")
         key = (B, str(dev))
         stash = self._value_stash.get(key)
         if stash is None:
@@ -322,8 +319,7 @@ class TransformerActorCritic(nn.Module):
         written, actions [n_max][E] int8 (optional) receives the trace (-1 past an env's end).
         Env e is greedy iff greedy_stride > 0 and e % greedy_stride == 0, else it samples with
         counters offset + t * offset_stride + e (+ *offset_dev)."""
-        if self._packed is None:
-            self.packed_weights()
+        self._ensure_packed()
         E, dev = env.E, env.device
         if actions is not None:
             if actions.dim() != 2:
@@ -333,9 +329,8 @@ class TransformerActorCritic(nn.Module):
         if n_max is None:
             raise ValueError("decode_steps: pass n_max or an actions buffer")
         check_out(obs2, "obs2", torch.float32, (2, E), dev, (cfg.SEQ_LEN, cfg.STATE_DIM))
-        if rowproj is not None and (rowproj.numel() < LIB.uavhip_policy_rowproj_floats(E) or
-                                    rowproj.dtype != torch.float32 or not rowproj.is_contiguous()):
-            raise ValueError("rowproj: need a contiguous float32 rowproj_buffer(E)")
+        if rowproj is not None:
+            _check_ring(rowproj, E, "E")
         check_out(steps, "steps", torch.int32, (E,), dev)
         check_out(finished, "finished", torch.uint8, (E,), dev)
         check_out(ep_return, "ep_return", torch.float64, (E,), dev)

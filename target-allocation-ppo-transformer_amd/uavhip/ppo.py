@@ -67,7 +67,7 @@ def ppo_diagnostics(old_logp, new_logp, old_values, new_values, returns, eps_cli
     _lib.DIAG). All arithmetic in double, fixed reduction order (bitwise repeatable, capturable).
     partials: a float64 workspace of uavhip_ppo_diagnostics_partials(n) elements (allocated if None)."""
     from . import _lib
-    from .vec_env import check_out
+    from ._lib import check_out
     dev = old_logp.device
     if dev.type != "cuda":
         raise RuntimeError("ppo_diagnostics runs on the GPU (HIP) only")

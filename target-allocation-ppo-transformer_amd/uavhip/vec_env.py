@@ -9,31 +9,42 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import LIB, check, ptr, stream_handle
+from ._lib import LIB, check, check_out, out_buf, ptr, stream_handle
 from .config import cfg as default_cfg, gen_vector, params_vector
 
 SCENE_KEYS_F64 = ("uav_pos", "uav_vel", "uav_load", "uav_cost", "tgt_pos", "tgt_vel", "tgt_value", "nfz_pos",
                   "icp_pos", "icp_vel")
 
 
-def _same_device(t, device):
-    return t.device.type == device.type and (device.index is None or t.device.index == device.index)
+# The wrappers' argument handling is module-level: their checks run on any object with the attributes
+# they read (E, N, M, device, obs_dtype), before any device call.
+def _rows_args(fn, E, stride, rows, **non_negative):
+    """The row arguments refine_assignments and search_assignments (`fn`) share: row s on the scene
+    of env s * stride, `rows` of them (None: every stride-th of the E envs), and the caps, each
+    >= 0. -> the number of rows."""
+    if stride < 1:
+        raise ValueError(f"{fn}: stride={stride} must be >= 1")
+    S = (E - 1) // stride + 1 if rows is None else int(rows)
+    if S < 1 or (S - 1) * stride >= E:
+        raise ValueError(f"{fn}: rows={S} at stride={stride} do not fit E={E}")
+    for name, cap in non_negative.items():
+        if cap < 0:
+            raise ValueError(f"{fn}: {name}={cap} must be >= 0")
+    return S
 
 
-def check_out(t, name, dtype, lead, device, tail=()):
-    """A caller-provided kernel buffer (read or written through a raw pointer): right device and
-    dtype, contiguous, exactly prod(lead + tail) elements -- anything else would be an out-of-bounds
-    or misread device access the C side cannot detect. None passes (NULL = not wanted)."""
-    if t is None:
-        return
-    n = 1
-    for d in tuple(lead) + tuple(tail):
-        n *= int(d)
-    if not isinstance(t, torch.Tensor) or not _same_device(t, device) or t.dtype != dtype or \
-            not t.is_contiguous() or t.numel() != n:
-        got = (f"{t.dtype} {tuple(t.shape)} on {t.device}, contiguous={t.is_contiguous()}"
-               if isinstance(t, torch.Tensor) else type(t).__name__)
-        raise ValueError(f"{name}: need a contiguous {dtype} tensor of {n} elements on {device} (got {got})")
+def _rows_bufs(S, N, n_stats, dev, assignment, out, J, covered, stats):
+    """Their buffers: the given `assignment` checked, the four outputs given or allocated."""
+    check_out(assignment, "assignment", torch.int32, (S, N), dev)
+    return (out_buf(out, "out", torch.int32, (S, N), dev), out_buf(J, "J", torch.float64, (S,), dev),
+            out_buf(covered, "covered", torch.int32, (S,), dev), out_buf(stats, "stats", torch.int32, (S, n_stats), dev))
+
+
+def _totals(E, dev, steps, finished, ep_return):
+    """The per-env totals teacher_steps / expert_steps add to: zeroed unless given."""
+    return (out_buf(steps, "steps", torch.int32, (E,), dev, zero=True),
+            out_buf(finished, "finished", torch.uint8, (E,), dev, zero=True),
+            out_buf(ep_return, "ep_return", torch.float64, (E,), dev, zero=True))
 
 
 class VecUAVEnv:
@@ -235,14 +246,10 @@ class VecUAVEnv:
         if K <= 0 or self.E % K:
             raise ValueError(f"select_best: K={K} must be > 0 and divide E={self.E}")
         S, dev = self.E // K, self.device
-        best = torch.empty(S, dtype=torch.int32, device=dev) if best is None else best
-        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
-        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
-        assignment = torch.empty(S, self.N, dtype=torch.int32, device=dev) if assignment is None else assignment
-        check_out(best, "best", torch.int32, (S,), dev)
-        check_out(J, "J", torch.float64, (S,), dev)
-        check_out(covered, "covered", torch.int32, (S,), dev)
-        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
+        best = out_buf(best, "best", torch.int32, (S,), dev)
+        J = out_buf(J, "J", torch.float64, (S,), dev)
+        covered = out_buf(covered, "covered", torch.int32, (S,), dev)
+        assignment = out_buf(assignment, "assignment", torch.int32, (S, self.N), dev)
         check(LIB.uavhip_select_best(self.desc, K, ptr(best), ptr(J), ptr(covered), ptr(assignment), stream_handle()),
               "uavhip_select_best")
         return best, J, covered, assignment
@@ -257,23 +264,8 @@ class VecUAVEnv:
         stats [rows, 4] int32: sweeps, moves, converged, invalid input ids). out may be `assignment`
         itself (in place). The env is only read."""
         stride, max_sweeps = int(stride), int(max_sweeps)
-        if stride < 1:
-            raise ValueError(f"refine_assignments: stride={stride} must be >= 1")
-        S = (self.E - 1) // stride + 1 if rows is None else int(rows)
-        if S < 1 or (S - 1) * stride >= self.E:
-            raise ValueError(f"refine_assignments: rows={S} at stride={stride} do not fit E={self.E}")
-        if max_sweeps < 0:
-            raise ValueError(f"refine_assignments: max_sweeps={max_sweeps} must be >= 0")
-        dev = self.device
-        out = torch.empty(S, self.N, dtype=torch.int32, device=dev) if out is None else out
-        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
-        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
-        stats = torch.empty(S, 4, dtype=torch.int32, device=dev) if stats is None else stats
-        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
-        check_out(out, "out", torch.int32, (S, self.N), dev)
-        check_out(J, "J", torch.float64, (S,), dev)
-        check_out(covered, "covered", torch.int32, (S,), dev)
-        check_out(stats, "stats", torch.int32, (S, 4), dev)
+        S = _rows_args("refine_assignments", self.E, stride, rows, max_sweeps=max_sweeps)
+        out, J, covered, stats = _rows_bufs(S, self.N, 4, self.device, assignment, out, J, covered, stats)
         check(LIB.uavhip_refine_assignments(self.desc, stride, S, max_sweeps, ptr(assignment), ptr(out), ptr(J),
                                             ptr(covered), ptr(stats), stream_handle()), "uavhip_refine_assignments")
         return out, J, covered, stats
@@ -288,25 +280,8 @@ class VecUAVEnv:
         converged, invalid input ids, exchanges made, 1 if the last scan found no improving pair).
         max_exchanges = 0 is refine_assignments, bitwise. The env is only read."""
         stride, max_exchanges, max_sweeps = int(stride), int(max_exchanges), int(max_sweeps)
-        if stride < 1:
-            raise ValueError(f"search_assignments: stride={stride} must be >= 1")
-        S = (self.E - 1) // stride + 1 if rows is None else int(rows)
-        if S < 1 or (S - 1) * stride >= self.E:
-            raise ValueError(f"search_assignments: rows={S} at stride={stride} do not fit E={self.E}")
-        if max_exchanges < 0:
-            raise ValueError(f"search_assignments: max_exchanges={max_exchanges} must be >= 0")
-        if max_sweeps < 0:
-            raise ValueError(f"search_assignments: max_sweeps={max_sweeps} must be >= 0")
-        dev = self.device
-        out = torch.empty(S, self.N, dtype=torch.int32, device=dev) if out is None else out
-        J = torch.empty(S, dtype=torch.float64, device=dev) if J is None else J
-        covered = torch.empty(S, dtype=torch.int32, device=dev) if covered is None else covered
-        stats = torch.empty(S, 6, dtype=torch.int32, device=dev) if stats is None else stats
-        check_out(assignment, "assignment", torch.int32, (S, self.N), dev)
-        check_out(out, "out", torch.int32, (S, self.N), dev)
-        check_out(J, "J", torch.float64, (S,), dev)
-        check_out(covered, "covered", torch.int32, (S,), dev)
-        check_out(stats, "stats", torch.int32, (S, 6), dev)
+        S = _rows_args("search_assignments", self.E, stride, rows, max_exchanges=max_exchanges, max_sweeps=max_sweeps)
+        out, J, covered, stats = _rows_bufs(S, self.N, 6, self.device, assignment, out, J, covered, stats)
         check(LIB.uavhip_search_assignments(self.desc, stride, S, max_exchanges, max_sweeps, ptr(assignment), ptr(out),
                                             ptr(J), ptr(covered), ptr(stats), stream_handle()),
               "uavhip_search_assignments")
@@ -333,27 +308,15 @@ class VecUAVEnv:
             raise ValueError("teacher_steps: assignment is required ([E, N] int32 target ids or -1)")
         E, dev = self.E, self.device
         lead = (n_max, E)
-        f64 = dict(dtype=torch.float64, device=dev)
-        obs = torch.empty(*lead, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev) if obs is None else obs
-        actions = torch.empty(*lead, dtype=torch.int8, device=dev) if actions is None else actions
-        reward = torch.empty(*lead, **f64) if reward is None else reward
-        done = torch.empty(*lead, dtype=torch.uint8, device=dev) if done is None else done
-        if info is None and want_info:
-            info = torch.empty(*lead, _lib.INFO_COUNT, **f64)
-        steps = torch.zeros(E, dtype=torch.int32, device=dev) if steps is None else steps
-        finished = torch.zeros(E, dtype=torch.uint8, device=dev) if finished is None else finished
-        ep_return = torch.zeros(E, **f64) if ep_return is None else ep_return
-        stats = torch.empty(E, 2, dtype=torch.int32, device=dev) if stats is None else stats
         check_out(assignment, "assignment", torch.int32, (E, self.N), dev)
-        check_out(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
-        check_out(actions, "actions", torch.int8, lead, dev)
-        check_out(reward, "reward", torch.float64, lead, dev)
-        check_out(done, "done", torch.uint8, lead, dev)
-        check_out(info, "info", torch.float64, lead, dev, (_lib.INFO_COUNT,))
-        check_out(steps, "steps", torch.int32, (E,), dev)
-        check_out(finished, "finished", torch.uint8, (E,), dev)
-        check_out(ep_return, "ep_return", torch.float64, (E,), dev)
-        check_out(stats, "stats", torch.int32, (E, 2), dev)
+        obs = out_buf(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
+        actions = out_buf(actions, "actions", torch.int8, lead, dev)
+        reward = out_buf(reward, "reward", torch.float64, lead, dev)
+        done = out_buf(done, "done", torch.uint8, lead, dev)
+        if info is not None or want_info:
+            info = out_buf(info, "info", torch.float64, lead, dev, (_lib.INFO_COUNT,))
+        steps, finished, ep_return = _totals(E, dev, steps, finished, ep_return)
+        stats = out_buf(stats, "stats", torch.int32, (E, 2), dev)
         check(LIB.uavhip_teacher_steps(self.desc, ptr(assignment), n_max, ptr(obs), ptr(actions), ptr(reward),
                                        ptr(done), ptr(info), ptr(steps), ptr(finished), ptr(ep_return), ptr(stats),
                                        stream_handle()), "uavhip_teacher_steps")
@@ -387,29 +350,16 @@ class VecUAVEnv:
         if n_max < 1:
             raise ValueError(f"expert_steps: n_max={n_max} must be >= 1")
         lead = (n_max, E)
-        f64 = dict(dtype=torch.float64, device=dev)
         check_out(actions, "actions", torch.int8, lead, dev)
         check_out(follow, "follow", torch.uint8, (E,), dev)
-        obs = torch.empty(*lead, _lib.SEQ_LEN, _lib.STATE_DIM, dtype=torch.float32, device=dev) if obs is None else obs
-        actions_out = torch.empty(*lead, dtype=torch.int8, device=dev) if actions_out is None else actions_out
-        labels = torch.empty(*lead, dtype=torch.int8, device=dev) if labels is None else labels
-        margin = torch.empty(*lead, **f64) if margin is None else margin
-        reward = torch.empty(*lead, **f64) if reward is None else reward
-        done = torch.empty(*lead, dtype=torch.uint8, device=dev) if done is None else done
-        steps = torch.zeros(E, dtype=torch.int32, device=dev) if steps is None else steps
-        finished = torch.zeros(E, dtype=torch.uint8, device=dev) if finished is None else finished
-        ep_return = torch.zeros(E, **f64) if ep_return is None else ep_return
-        stats = torch.empty(E, 3, dtype=torch.int32, device=dev) if stats is None else stats
-        check_out(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
-        check_out(actions_out, "actions_out", torch.int8, lead, dev)
-        check_out(labels, "labels", torch.int8, lead, dev)
-        check_out(margin, "margin", torch.float64, lead, dev)
-        check_out(reward, "reward", torch.float64, lead, dev)
-        check_out(done, "done", torch.uint8, lead, dev)
-        check_out(steps, "steps", torch.int32, (E,), dev)
-        check_out(finished, "finished", torch.uint8, (E,), dev)
-        check_out(ep_return, "ep_return", torch.float64, (E,), dev)
-        check_out(stats, "stats", torch.int32, (E, 3), dev)
+        obs = out_buf(obs, "obs", torch.float32, lead, dev, (_lib.SEQ_LEN, _lib.STATE_DIM))
+        actions_out = out_buf(actions_out, "actions_out", torch.int8, lead, dev)
+        labels = out_buf(labels, "labels", torch.int8, lead, dev)
+        margin = out_buf(margin, "margin", torch.float64, lead, dev)
+        reward = out_buf(reward, "reward", torch.float64, lead, dev)
+        done = out_buf(done, "done", torch.uint8, lead, dev)
+        steps, finished, ep_return = _totals(E, dev, steps, finished, ep_return)
+        stats = out_buf(stats, "stats", torch.int32, (E, 3), dev)
         check(LIB.uavhip_expert_steps(self.desc, ptr(actions), ptr(follow), n_max, ptr(obs), ptr(actions_out),
                                       ptr(labels), ptr(margin), ptr(reward), ptr(done), ptr(steps), ptr(finished),
                                       ptr(ep_return), ptr(stats), stream_handle()), "uavhip_expert_steps")

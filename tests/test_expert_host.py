@@ -10,6 +10,7 @@ import itertools
 import numpy as np
 import pytest
 
+import capi_host
 from test_refine_host import RTOL_J, SHAPES, _env_desc, host_scenes, prm, refine_np
 
 CASES = SHAPES + [(8, 128, 4)]      # (N, M, E); the last two: two targets per lane
@@ -23,11 +24,7 @@ def gpu_cases():
     return out + [(16, 32, 32, 2.0)]
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    """Everything here restates or calls one entry point: without it in the library it means nothing."""
-    from uavhip import _lib
-    assert "uavhip_expert_steps" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_expert_steps")
+_entry_point = capi_host._entry_point("uavhip_expert_steps")
 
 
 def expert_np(scene, omega, trace=None, tables=None, flip=None):

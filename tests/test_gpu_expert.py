@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import capi_host
 from conftest import has_gpu
 from test_expert_host import expert_np, flipped_traces, gpu_cases, trace_array
 from test_gpu_solve import gpu_policy
@@ -24,10 +25,7 @@ PER_STEP = ("obs", "actions", "labels", "margin", "reward", "done")  # [n_max, E
 PER_ENV = ("steps", "finished", "ep_return", "stats")                # [E, ...]
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    from uavhip import _lib
-    assert "uavhip_expert_steps" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_expert_steps")
+_entry_point = capi_host._entry_point("uavhip_expert_steps")
 
 
 @functools.lru_cache(maxsize=None)

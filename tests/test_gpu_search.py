@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import capi_host
 from test_gpu_refine import decoded_env, make_env, tables
 from test_gpu_solve import gpu_policy
 from test_refine_host import OMEGAS, RTOL_J, host_scenes, random_starts
@@ -27,10 +28,7 @@ pytestmark = pytest.mark.gpu
 CASES = [(s, True) for s in SHAPES] + [(NOTHING_TO_DO, False), ((8, 128, 3), None), ((17, 20, 5), None)]
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    from uavhip import _lib
-    assert "uavhip_search_assignments" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_search_assignments")
+_entry_point = capi_host._entry_point("uavhip_search_assignments")
 
 
 def run_and_compare(label, env, omega, start, stride=1, rows=None, max_exchanges=CAPS[0], max_sweeps=CAPS[1], **kw):

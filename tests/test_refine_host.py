@@ -10,17 +10,16 @@ import random
 import numpy as np
 import pytest
 
+import capi_host
+from capi_host import _env_desc
+
 RTOL_J = 1e-12  # the project's reward bar
 SHAPES = [(4, 4, 6), (5, 7, 33), (16, 32, 32), (33, 34, 3), (3, 70, 5)]  # (N, M, E); the last: two targets per lane
 OMEGAS = (0.0, 0.5)
 SCENE_SEED, START_SEED = 7, 1
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    """Everything here restates or calls one entry point: without it in the library it means nothing."""
-    from uavhip import _lib
-    assert "uavhip_refine_assignments" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_refine_assignments")
+_entry_point = capi_host._entry_point("uavhip_refine_assignments")
 
 
 def refine_np(p_dmg, p_pen, value, cost, tgt_id, omega, start=None, max_sweeps=32):
@@ -224,17 +223,6 @@ def test_gpu_case_conditions_on_oracle_tables():
         runs = [refine_rows(pd, pp, v, c, ids, omega, st) for st in (None, random_starts(N, M, E))]
         to_none = check_case_conditions(f"({N}, {M}, {E}) omega {omega}", runs)
         assert omega == 0.0 or to_none > 0
-
-
-def _env_desc(N=8, M=4, E=6):
-    from uavhip import _lib
-    d = _lib.EnvDesc()
-    d.E, d.N, d.M, d.Kn, d.Ki, d.scene_buffers = E, N, M, 1, 1, 1
-    for name in ("uav_pos", "uav_vel", "uav_load", "uav_cost", "tgt_pos", "tgt_vel", "tgt_value", "tgt_id", "nfz_pos",
-                 "icp_pos", "icp_vel", "p_dmg", "p_pen", "istate", "nh_final", "nh_pure", "t_cost", "n_lock",
-                 "assigned", "dstate", "window"):
-        setattr(d, name, 16)  # non-NULL placeholders: validation never dereferences them
-    return d
 
 
 def test_refine_argument_checks_without_gpu():

@@ -9,6 +9,7 @@ import itertools
 import numpy as np
 import pytest
 
+import capi_host
 from test_refine_host import (OMEGAS, RTOL_J, J_of, _env_desc, host_scenes, prm, random_starts, refine_np)
 
 # (N, M, E): every one has a row that makes an exchange; the last two have two targets per lane
@@ -17,11 +18,7 @@ NOTHING_TO_DO = (4, 4, 6)  # no row makes an exchange
 CAPS = (32, 32)            # max_exchanges, max_sweeps
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    """Everything here restates or calls one entry point: without it in the library it means nothing."""
-    from uavhip import _lib
-    assert "uavhip_search_assignments" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_search_assignments")
+_entry_point = capi_host._entry_point("uavhip_search_assignments")
 
 
 def best_exchange(P, v, wc, a):

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from capi_host import _env_desc
+
 
 def select_best_np(uav_idx, J, covered, assigned, tgt_id, N, K):
     """uavhip_select_best restated (include/uavhip.h): envs e = s * K + k; per scene the FINISHED
@@ -52,17 +54,6 @@ def test_select_best_restatement():
     # a finished replica with a negative J still beats "none"
     b, j, _, _ = select_best_np(np.array([3, 0]), np.array([-2.0, 5.0]), covered[:2], assigned[:2], tgt_id[:2], N, 2)
     assert b.tolist() == [0] and j.tolist() == [-2.0]
-
-
-def _env_desc(N=8, M=4, E=4, flags=0):
-    from uavhip import _lib
-    d = _lib.EnvDesc()
-    d.E, d.N, d.M, d.Kn, d.Ki, d.scene_buffers, d.flags = E, N, M, 1, 1, 1, flags
-    for name in ("uav_pos", "uav_vel", "uav_load", "uav_cost", "tgt_pos", "tgt_vel", "tgt_value", "tgt_id", "nfz_pos",
-                 "icp_pos", "icp_vel", "p_dmg", "p_pen", "istate", "nh_final", "nh_pure", "t_cost", "n_lock",
-                 "assigned", "dstate", "window"):
-        setattr(d, name, 16)  # non-NULL placeholders: validation never dereferences them
-    return d
 
 
 def _policy_desc():

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import capi_host
 from test_refine_host import _env_desc, host_scenes, prm, random_starts
 
 E = 64
@@ -16,10 +17,7 @@ OMEGA_REJECT = 2.0
 TEACHER_SEED = 1  # random_starts' seed: at OMEGA_REJECT every shape shows rejected assigns (checked below)
 
 
-@pytest.fixture(autouse=True, scope="module")
-def _entry_point():
-    from uavhip import _lib
-    assert "uavhip_teacher_steps" in _lib.EXPORTS and hasattr(_lib.LIB, "uavhip_teacher_steps")
+_entry_point = capi_host._entry_point("uavhip_teacher_steps")
 
 
 def teach_indices(tgt_id, assignment):

@@ -3,16 +3,7 @@ returns UAVHIP_EINVAL with a message before any HIP call, as test_rollout_step_a
 expects of uavhip_rollout_step."""
 import ctypes
 
-
-def _env_desc(N=8):
-    from uavhip import _lib
-    d = _lib.EnvDesc()
-    d.E, d.N, d.M, d.Kn, d.Ki, d.scene_buffers = 4, N, 4, 1, 1, 1
-    for name in ("uav_pos", "uav_vel", "uav_load", "uav_cost", "tgt_pos", "tgt_vel", "tgt_value", "tgt_id", "nfz_pos",
-                 "icp_pos", "icp_vel", "p_dmg", "p_pen", "istate", "nh_final", "nh_pure", "t_cost", "n_lock",
-                 "assigned", "dstate", "window"):
-        setattr(d, name, 16)  # non-NULL placeholders: validation never dereferences them
-    return d
+from capi_host import _env_desc
 
 
 def test_rollout_actor_steps_argument_checks_without_gpu():
