@@ -490,6 +490,50 @@ int uavhip_search_assignments(const uavhip_env* env, int32_t env_stride, int32_t
                               int32_t max_sweeps, const int32_t* assignment_in, int32_t* assignment_out,
                               double* J, int32_t* covered, int32_t* stats, uavhip_stream_t stream);
 
+/* The exchange-move search under constraints (k_search_constrained, search_constrained.hip): pairs
+ * that may not be flown, UAVs that keep the target they came with (a plan partly executed), and a
+ * limit on the UAVs of one target. Notation, g, Qo, the id conversion, J, covered and the termination
+ * argument are uavhip_search_assignments'; nothing contracted. The constraint arrays are indexed by
+ * ROW s (not by env) and their columns are in LIST order, as p_dmg's; a NULL array constrains nothing:
+ *   allowed  [S][N][M] u8   nonzero = UAV u may take list-order target t        (NULL: every pair)
+ *   fixed    [S][N]    u8   nonzero = UAV u keeps its input target, or none      (NULL: no UAV)
+ *   capacity [S][M]    i32  the most UAVs on list-order target t; < 0 counts as 0 (NULL: no limit)
+ * With n[t] the UAVs counted on t so far:
+ *
+ *   START: a <- assignment_in converted exactly as uavhip_refine_assignments converts it (a fixed UAV
+ *          whose id matches no tgt_id is fixed to none); n <- 0; dropped <- 0; fixed_conflicts <- 0
+ *     pass 1, the fixed u in ascending order with a[u] >= 0: u keeps a[u] whatever the other
+ *            constraints say;  fixed_conflicts += 1 if !allowed[u][a[u]];
+ *            fixed_conflicts += 1 if n[a[u]] >= capacity[a[u]];  n[a[u]] += 1
+ *     pass 2, the free u in ascending order with a[u] >= 0: if !allowed[u][a[u]] or
+ *            n[a[u]] >= capacity[a[u]]: a[u] <- -1, dropped += 1; else n[a[u]] += 1
+ *   PHASE: uavhip_refine_assignments' sweep with two changes. A fixed u is skipped: no visit, no
+ *          move. For a free u the candidates are -1 and the targets t with allowed[u][t] and
+ *          (t == a[u] or the number of OTHER UAVs on t < capacity[t]); among them the rule is the
+ *          sweep's own: g[t] = (v[t] * Q[t]) * P[u][t] - (w * c[u]), the candidate is the lowest
+ *          index attaining the maximum if that maximum is > 0.0, else -1 (gain 0.0), and u moves
+ *          iff the gain is strictly greater than g[a[u]]. (a[u] of a free u is always a candidate.)
+ *   SCAN:  uavhip_search_assignments' scan over the pairs i < j with both UAVs free, a[i] != a[j],
+ *          (s == -1 or allowed[j][s]) and (t == -1 or allowed[i][t]), s = a[i], t = a[j]; d(i, j),
+ *          its order of operations and the tie-break are unchanged. A swap keeps every target's
+ *          count, so capacity is not looked at.
+ *   The loop of phases, scans and exchanges, max_exchanges and max_sweeps are
+ *   uavhip_search_assignments'.
+ * Guarantees: every free UAV's output pair is allowed; no target holds more UAVs, free and fixed,
+ * than max(capacity[t], its fixed UAVs); a fixed UAV leaves as it came. With the three arrays NULL,
+ * and with neutral arrays (allowed all nonzero, fixed all zero, capacity >= N), every output is
+ * bitwise uavhip_search_assignments', and stats[:, :6] is its stats.
+ *  - env, env_stride, S, max_exchanges, max_sweeps, assignment_in (nullable), assignment_out (required;
+ *    may alias assignment_in), J, covered (required): as uavhip_search_assignments, the same bounds;
+ *  - stats [S][8] int32 (nullable): the six of uavhip_search_assignments, dropped, fixed_conflicts.
+ * The full N <= 64, M <= 128 range. The env's state and scene and the constraint arrays are only
+ * read; no allocation, no atomics, no grid-wide synchronisation. */
+int uavhip_search_assignments_constrained(const uavhip_env* env, int32_t env_stride, int32_t S,
+                                          int32_t max_exchanges, int32_t max_sweeps, const uint8_t* allowed,
+                                          const uint8_t* fixed, const int32_t* capacity,
+                                          const int32_t* assignment_in, int32_t* assignment_out, double* J,
+                                          int32_t* covered, int32_t* stats, uavhip_stream_t stream);
+
 /* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
  * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
  * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is

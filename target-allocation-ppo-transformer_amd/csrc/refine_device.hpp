@@ -1,7 +1,8 @@
 // refine_device.hpp -- the device side of the best-response local search on J(X), shared by k_refine
-// (refine.hip, uavhip_refine_assignments) and k_search (search.hip, uavhip_search_assignments): one
-// wave's view of one row -- the scene's registers, the id conversion, the sweeps and the scoring of
-// the result. Both translation units are built with -ffp-contract=off; the rule is in
+// (refine.hip, uavhip_refine_assignments), k_search (search.hip, uavhip_search_assignments) and
+// k_search_constrained (search_constrained.hip, uavhip_search_assignments_constrained): one wave's
+// view of one row -- the scene's registers, the id conversion, the sweeps and the scoring of the
+// result. All three translation units are built with -ffp-contract=off; the rule is in
 // include/uavhip.h.
 //
 // One wave per row. Lane t owns target t (and t + 64 when M > 64): its value, its id and the running
@@ -40,7 +41,19 @@ __device__ __forceinline__ double wave_sum(double x) {
     return x;
 }
 
-template <int TPL, int NCAP>
+// What uavhip_search_assignments_constrained adds to a row (LIM): lane t holds, per target slot, the
+// UAVs that may take it and its capacity; `fixed` is wave-uniform. RefineRow's default holds nothing
+// and its sweeps are the unconstrained ones, instruction for instruction.
+template <int TPL, bool LIM>
+struct RowLimits {};
+template <int TPL>
+struct RowLimits<TPL, true> {
+    unsigned long long ok[TPL];  // bit u: allowed[u][t] of the lane's targets
+    int cap[TPL];                // capacity[t] of the lane's targets, >= 0
+    unsigned long long fixed;    // bit u: UAV u is fixed
+};
+
+template <int TPL, int NCAP, bool LIM = false>
 struct RefineRow {
     static_assert(NCAP == 0 || TPL == 1, "the register column is the one-target-per-lane path");
     int N, M, lane;
@@ -53,6 +66,7 @@ struct RefineRow {
     int a, invalid;                 // a[lane]: list index or -1; ids of the input that matched nothing
     double om[NCAP > 0 ? NCAP : 1];
     int sweeps, moves, converged;
+    RowLimits<TPL, LIM> lim;
 
     // the scene of env s * stride (its active buffer) into registers; every UAV at -1
     __device__ __forceinline__ void load(const uavhip_env& env, int s, int stride, int lane_) {
@@ -148,13 +162,20 @@ struct RefineRow {
     }
 
     // best-response sweeps from a, until a sweep makes no move or max_sweeps sweeps of this call
-    // have run; sweeps and moves accumulate over calls, converged is this call's
+    // have run; sweeps and moves accumulate over calls, converged is this call's. With LIM a fixed
+    // UAV is not visited, and a free one chooses among the targets it may take that have room
+    // (cnt, the other UAVs on t, < cap) or are its own.
     __device__ __forceinline__ void phase(int max_sweeps) {
         const long long last = (long long)sweeps + max_sweeps;
         converged = 1;
         while (sweeps < last) {
             int moved = 0;
             for (int u = 0; u < N; ++u) {
+                int own = -1;
+                if constexpr (LIM) {
+                    if (lim.fixed >> u & 1) continue;
+                    own = readlane_i(a, u);
+                }
                 double Q[TPL];
                 int cnt[TPL];
                 build_q(u, Q, cnt);
@@ -169,7 +190,9 @@ struct RefineRow {
                     if (t < M) {
                         const double p = pd[u * M + t] * pu;
                         g[j] = (v[j] * Q[j]) * p - wcu;
-                        if (g[j] > bg) {
+                        bool may = true;
+                        if constexpr (LIM) may = (lim.ok[j] >> u & 1) && (t == own || cnt[j] < lim.cap[j]);
+                        if (may && g[j] > bg) {
                             bg = g[j];
                             bt = t;
                         }
@@ -229,7 +252,7 @@ struct RefineRow {
     }
 };
 
-// ------------------------------------------------------------------ host: what the two entry points share
+// ------------------------------------------------------------------ host: what the entry points share
 // The env and the rows of entry point `fn` (row s < S on the scene of env s * env_stride), and the rest
 // of its arguments: `rest_ok`, with `caps` (a format and its values) naming the caps in the message.
 inline int check_rows(const char* fn, const uavhip_env* env, int32_t env_stride, int32_t S, bool rest_ok,

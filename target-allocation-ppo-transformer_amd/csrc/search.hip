@@ -6,32 +6,13 @@
 // bit with a Python restatement of the rule.
 //
 // One wave per row, four per workgroup; the row's registers and the sweeps are RefineRow
-// (refine_device.hpp), k_refine's own. The scan over the pairs, per lane u < N once per scan:
-//   Po[u] = P[u][a[u]]                                                     (one gathered load)
-//   Qo[u] = product of (1.0 - Po[k]) over k != u with a[k] == a[u], ascending k
-//           (N readlanes of a[k] and 1.0 - Po[k], a predicated multiply each)
-//   vt[u] = v[a[u]]                                                        (a shuffle)
-//   gown[u] = g(u, a[u], Qo[u])
-// then a uniform loop over i: lane j > i evaluates d(i, j) from the uniform a[i], Qo[i], gown[i],
-// v[a[i]], p_pen[i], w c[i], its own a[j], Qo[j], gown[j], vt[j], p_pen[j], w c[j] and two gathered
-// loads, p_dmg[j][a[i]] and p_dmg[i][a[j]] -- about N gathered loads per UAV and scan. The lane keeps
-// its best over i (strict >: the lowest i), a six-step butterfly on (d, i, j) the lowest (i, j)
-// among equal d. No LDS, no atomics, nothing shared between waves; the env and the scene are only read.
-#include "refine_device.hpp"
+// (refine_device.hpp), k_refine's own; the scan over the pairs is best_exchange
+// (search_device.hpp), which k_search_constrained (search_constrained.hip) runs too. No LDS, no
+// atomics, nothing shared between waves; the env and the scene are only read.
+#include "search_device.hpp"
 
 namespace uavhip {
 namespace {
-
-// value of target t >= 0 from the lanes that own it, t per lane
-template <int TPL>
-__device__ __forceinline__ double value_of(const double (&v)[TPL], int t) {
-    double x = __shfl(v[0], t & (kWave - 1));
-    if constexpr (TPL == 2) {
-        const double hi = __shfl(v[1], t & (kWave - 1));
-        x = t >= kWave ? hi : x;
-    }
-    return x;
-}
 
 template <int TPL, int NR>
 __global__ __launch_bounds__(64 * kRefineWaves) void k_search(uavhip_env env, int stride, int S, int max_exchanges,
@@ -44,66 +25,13 @@ __global__ __launch_bounds__(64 * kRefineWaves) void k_search(uavhip_env env, in
     r.load(env, s, stride, lane);
     r.convert(ain, s);
     r.load_columns();
-    const int N = r.N, M = r.M;
-
     int exchanges = 0, scan_clean = 0;
     for (;;) {
         r.phase(max_sweeps);
         if (max_exchanges == 0) break;
-
-        // per-UAV terms of this scan
-        const int t = r.isu ? r.a : -1;
-        const int tc = t < 0 ? 0 : t;  // a valid index for the loads and shuffles of an idle lane
-        const double Po = t >= 0 ? r.pd[lane * M + tc] * r.pen : 0.0;
-        const double omo = 1.0 - Po;
-        double Qo = 1.0;
-        for (int k = 0; k < N; ++k) {
-            const int ak = readlane_i(t, k);
-            if (ak < 0) continue;
-            const double ok = readlane_d(omo, k);
-            if (ak == t && k != lane) Qo = Qo * ok;
-        }
-        const double vt = value_of<TPL>(r.v, tc);
-        const double vq = vt * Qo;
-        const double gown = t >= 0 ? vq * Po - r.wc : 0.0;
-
-        double bd = -__builtin_huge_val();
-        int bi = 0x7fffffff;
-        for (int i = 0; i + 1 < N; ++i) {
-            const int si = readlane_i(t, i);
-            const int sc = si < 0 ? 0 : si;
-            const double Qi = readlane_d(Qo, i), gi = readlane_d(gown, i);
-            const double peni = readlane_d(r.pen, i), wci = readlane_d(r.wc, i);
-            double vs;
-            if constexpr (TPL == 2)
-                vs = readlane_d(sc >= kWave ? r.v[1] : r.v[0], sc & (kWave - 1));
-            else
-                vs = readlane_d(r.v[0], sc);
-            if (lane > i && lane < N && t != si) {
-                // j = lane takes s = a[i], i takes t = a[j]
-                const double gjs = si >= 0 ? (vs * Qi) * (r.pd[lane * M + sc] * r.pen) - r.wc : 0.0;
-                const double git = t >= 0 ? vq * (r.pd[i * M + tc] * peni) - wci : 0.0;
-                const double d = (gjs + git) - (gi + gown);
-                if (d > bd) {
-                    bd = d;
-                    bi = i;
-                }
-            }
-        }
-        int bj = lane;
-#pragma unroll
-        for (int m = 1; m < kWave; m <<= 1) {
-            const double d_o = __shfl_xor(bd, m);
-            const int i_o = __shfl_xor(bi, m), j_o = __shfl_xor(bj, m);
-            if (d_o > bd || (d_o == bd && (i_o < bi || (i_o == bi && j_o < bj)))) {
-                bd = d_o;
-                bi = i_o;
-                bj = j_o;
-            }
-        }
-        bd = readlane_d(bd, 0);
-        bi = readlane_i(bi, 0);
-        bj = readlane_i(bj, 0);
+        double bd;
+        int bi, bj;
+        best_exchange(r, bd, bi, bj);
         if (!(bd > 0.0)) {
             scan_clean = 1;
             break;

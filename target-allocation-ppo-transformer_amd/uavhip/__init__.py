@@ -26,7 +26,7 @@ from .vec_env import VecUAVEnv  # noqa: F401
 def __getattr__(name):
     # solve.py is also a command line (python -m uavhip.solve): imported on first use, so that runpy
     # does not find it in sys.modules already
-    if name in ("Allocation", "AllocationSolver"):
+    if name in ("Allocation", "AllocationSolver", "Constraints"):
         from . import solve
         return getattr(solve, name)
     if name == "TrainingRun":  # fit.py is a command line too (python -m uavhip.fit)
@@ -40,4 +40,4 @@ def __getattr__(name):
 
 __all__ = ["LIB", "UavHipError", "Config", "cfg", "TransformerActorCritic", "pack_weights", "PPOAgent", "gae",
            "RolloutEngine", "Trajectory", "VecUAVEnv", "load_checkpoint", "save_checkpoint", "Allocation",
-           "AllocationSolver", "TrainingRun", "ImitationRun", "TeacherBatch"]
+           "AllocationSolver", "Constraints", "TrainingRun", "ImitationRun", "TeacherBatch"]

@@ -128,6 +128,8 @@ _SIGS = {
                                                  _vp]),
     "uavhip_search_assignments": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                                  _vp, _vp]),
+    "uavhip_search_assignments_constrained": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _i32, _vp, _vp,
+                                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "uavhip_teacher_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
     "uavhip_expert_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

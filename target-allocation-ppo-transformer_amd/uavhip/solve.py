@@ -22,7 +22,9 @@ moves to the target, or to none, where its marginal contribution to J is largest
 and baseline() runs that search from the empty assignment -- the non-learned yardstick a
 checkpoint's mean J is read against. exchanges = X > 0 (solve and baseline) runs the search with a second
 neighbourhood instead (uavhip_search_assignments): where no single move improves J, the best swap of
-two UAVs' targets is made and the sweeps run again, at most X times.
+two UAVs' targets is made and the sweeps run again, at most X times. constraints = Constraints(...)
+(solve and baseline) runs that search under pairs that may not be flown, UAVs that are already committed
+and a limit on the UAVs of one target (uavhip_search_assignments_constrained); the decode ignores them.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
 [--refine SWEEPS] [--exchanges X] [--baseline] prints one JSON line (mean / best J, mean covered, mean steps,
@@ -57,12 +59,54 @@ class Allocation:
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
     decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
     refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
-    #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean
+    #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean;
+    #                                              [S, 8] with constraints: + pairs dropped, fixed conflicts
 
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
                             (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
                              self.actions, self.decoded_J, self.refine_stats)))
+
+
+@dataclass
+class Constraints:
+    """What solve(constraints=) / baseline(constraints=) hold the local search to, per scene s and in
+    the scene's LIST order of targets (as p_dmg's columns); None for "no such constraint". Tensors (or
+    arrays) of exactly these dtypes and shapes; they are moved to the solver's device."""
+    allowed: Optional[torch.Tensor] = None    # [S, N, M] uint8 / bool: nonzero = UAV u may take target t
+    capacity: Optional[torch.Tensor] = None   # [S, M] int32: the most UAVs on target t (< 0 counts as 0)
+    fixed_ids: Optional[torch.Tensor] = None  # [S, N] int32: -2 = free, -1 = fixed to none, else the target ID
+    #                                           (tgt_id) UAV u is committed to
+
+    def on(self, what, S, N, M, device):
+        """Checked against S scenes of N x M, before any device call; then on `device`:
+        (allowed uint8, capacity, fixed_ids) with None kept."""
+        out = []
+        for name, dtypes, shape in (("allowed", (torch.uint8, torch.bool), (S, N, M)),
+                                    ("capacity", (torch.int32,), (S, M)), ("fixed_ids", (torch.int32,), (S, N))):
+            t = getattr(self, name)
+            if t is not None:
+                t = torch.as_tensor(t)
+                if t.dtype not in dtypes or tuple(t.shape) != shape:
+                    raise ValueError(f"{what}: constraints.{name}: need {' or '.join(map(str, dtypes))} {shape} "
+                                     f"(got {t.dtype} {tuple(t.shape)})")
+            out.append(t)
+        return tuple(None if t is None else t.to(device=device, dtype=torch.uint8 if t.dtype == torch.bool else t.dtype)
+                     .contiguous() for t in out)
+
+
+def _check_constraints(what, constraints):
+    if constraints is not None and not isinstance(constraints, Constraints):
+        raise ValueError(f"{what}: constraints must be a uavhip.solve.Constraints (got {type(constraints).__name__})")
+
+
+def _with_fixed(assignment, fixed_ids, shape, device):
+    """(the start with the committed UAVs' ids written in, the fixed flags) of the constrained search."""
+    if fixed_ids is None:
+        return assignment, None
+    if assignment is None:
+        assignment = torch.full(shape, -1, dtype=torch.int32, device=device)
+    return torch.where(fixed_ids != -2, fixed_ids, assignment), (fixed_ids != -2).to(torch.uint8)
 
 
 class AllocationSolver:
@@ -154,7 +198,8 @@ class AllocationSolver:
         return env
 
     @torch.no_grad()
-    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0):
+    def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0,
+              constraints=None):
         """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
         `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
         greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
@@ -166,7 +211,13 @@ class AllocationSolver:
         refine = 0 launches nothing more and changes nothing.
         exchanges = X > 0 (needs refine > 0): the polish is uavhip_search_assignments with at most X
         pairwise exchanges and R sweeps per phase, refine_stats its [S, 6] counters. exchanges = 0 is
-        the plain refinement: the same launches, the same results."""
+        the plain refinement: the same launches, the same results.
+        constraints = Constraints(allowed, capacity, fixed_ids) (needs refine > 0): the DECODE IGNORES
+        THEM -- the policy walks the scene as ever. The solver then overwrites the decoded assignment of
+        every committed UAV (fixed_ids != -2) with its fixed id and polishes with
+        uavhip_search_assignments_constrained (at most X exchanges, X = 0 included), which drops what the
+        constraints do not admit and searches within them; refine_stats is its [S, 8] counters and
+        decoded_J stays the unconstrained decode's J. constraints = None changes no launch and no result."""
         refine, exchanges = int(refine), int(exchanges)
         if refine < 0:
             raise ValueError("solve: refine must be >= 0")
@@ -174,8 +225,13 @@ class AllocationSolver:
             raise ValueError("solve: exchanges must be >= 0")
         if exchanges > 0 and refine == 0:
             raise ValueError("solve: exchanges > 0 needs refine > 0 (the sweeps between the exchanges)")
+        _check_constraints("solve", constraints)
+        if constraints is not None and refine == 0:
+            raise ValueError("solve: constraints need refine > 0 (the decode ignores them; the search applies them)")
         scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
+        if constraints is not None:
+            allowed, capacity, fixed_ids = constraints.on("solve", S, self.N, self.M, self.device)
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
             n_max = int(self.N * self.M if max_steps is None else max_steps)
@@ -192,7 +248,11 @@ class AllocationSolver:
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
             if refine == 0:
                 return Allocation(assignment, J, covered, best, steps, replica_J, actions)
-            if exchanges > 0:
+            if constraints is not None:
+                start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
+                refined, rJ, rcov, stats = env.search_assignments_constrained(
+                    start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=refine)
+            elif exchanges > 0:
                 refined, rJ, rcov, stats = env.search_assignments(assignment, stride=K, rows=S, max_exchanges=exchanges,
                                                                   max_sweeps=refine)
             else:
@@ -200,20 +260,29 @@ class AllocationSolver:
         return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats)
 
     @torch.no_grad()
-    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0):
+    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0, constraints=None):
         """The non-learned yardstick for the same objective: the scenes solve() would run (scene for
         scene under the same `seed`), no policy launch, the best-response local search started from
         the empty assignment (a greedy constructor plus local search). Returns an Allocation whose
         decode-only fields (best_replica, steps, replica_J) are zeros. exchanges = X > 0: the search
-        with at most X pairwise exchanges (uavhip_search_assignments), refine_stats [S, 6]."""
+        with at most X pairwise exchanges (uavhip_search_assignments), refine_stats [S, 6].
+        constraints = Constraints(...): uavhip_search_assignments_constrained from the assignment that
+        holds the committed UAVs' fixed ids and nothing else, refine_stats [S, 8]."""
         exchanges = int(exchanges)
         if exchanges < 0:
             raise ValueError("baseline: exchanges must be >= 0")
+        _check_constraints("baseline", constraints)
         scenes, S, seed = self._scene_args("baseline", scenes, num_scenes, seed)
         K = self.K
+        if constraints is not None:
+            allowed, capacity, fixed_ids = constraints.on("baseline", S, self.N, self.M, self.device)
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
-            if exchanges > 0:
+            if constraints is not None:
+                start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
+                assignment, J, covered, stats = env.search_assignments_constrained(
+                    start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=max_sweeps)
+            elif exchanges > 0:
                 assignment, J, covered, stats = env.search_assignments(None, stride=K, rows=S, max_exchanges=exchanges,
                                                                        max_sweeps=max_sweeps)
             else:

@@ -287,6 +287,31 @@ class VecUAVEnv:
               "uavhip_search_assignments")
         return out, J, covered, stats
 
+    def search_assignments_constrained(self, assignment=None, allowed=None, fixed=None, capacity=None, stride=1,
+                                       rows=None, max_exchanges=32, max_sweeps=32, out=None, J=None, covered=None,
+                                       stats=None):
+        """uavhip_search_assignments_constrained: search_assignments under three constraints, each
+        indexed by ROW with its columns in list order (as p_dmg's), None for "no such constraint":
+        allowed [rows, N, M] uint8 (nonzero: the UAV may take the target), fixed [rows, N] uint8
+        (nonzero: the UAV keeps the target `assignment` gives it, or none) and capacity [rows, M]
+        int32 (the most UAVs on the target; < 0 counts as 0). A free UAV's input pair that is not
+        allowed, or whose target is full, is dropped before the search. Other arguments as
+        search_assignments. Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered
+        [rows] int32, stats [rows, 8] int32: search_assignments' six, pairs dropped at the start,
+        conflicts of the fixed UAVs with allowed / capacity). Without constraints, or with neutral
+        ones, it is search_assignments, bitwise. The env is only read."""
+        stride, max_exchanges, max_sweeps = int(stride), int(max_exchanges), int(max_sweeps)
+        S = _rows_args("search_assignments_constrained", self.E, stride, rows, max_exchanges=max_exchanges, max_sweeps=max_sweeps)
+        check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
+        out, J, covered, stats = _rows_bufs(S, self.N, 8, self.device, assignment, out, J, covered, stats)
+        check(LIB.uavhip_search_assignments_constrained(self.desc, stride, S, max_exchanges, max_sweeps, ptr(allowed),
+                                                        ptr(fixed), ptr(capacity), ptr(assignment), ptr(out), ptr(J),
+                                                        ptr(covered), ptr(stats), stream_handle()),
+              "uavhip_search_assignments_constrained")
+        return out, J, covered, stats
+
     def teacher_steps(self, assignment, n_max=None, obs=None, actions=None, reward=None, done=None, info=None,
                       steps=None, finished=None, ep_return=None, stats=None, want_info=False):
         """uavhip_teacher_steps: walk every env from its current state (reset it first) along
