@@ -534,6 +534,54 @@ int uavhip_search_assignments_constrained(const uavhip_env* env, int32_t env_str
                                           const int32_t* assignment_in, int32_t* assignment_out, double* J,
                                           int32_t* covered, int32_t* stats, uavhip_stream_t stream);
 
+/* The optimum of J(X) (k_exact_*, exact.hip): not a search but a subset DP over the UAVs, exact for
+ * N <= UAVHIP_EXACT_MAX_N. J is a sum over targets of a function of the SET of UAVs on that target, so
+ * with list-order targets t = 0..M-1, sets S, T of UAVs as N-bit integers (bit u = UAV u) and the
+ * notation of uavhip_refine_assignments (P, v, c, w):
+ *   val_t(T)   = v[t] (1 - prod_{u in T} (1 - P[u][t])) - w sum_{u in T} c[u]
+ *   D_0[S]     = 0                                                        for every S
+ *   D_{t+1}[S] = max over the feasible T <= S of  D_t[S \ T] + val_t(T)
+ *   J*         = D_M[all UAVs]
+ * 3^N steps per target. The feasible set is uavhip_search_assignments_constrained's guarantee: with F_t
+ * the fixed UAVs on t (fixed[u] != 0 and assignment_in[u] converts to t) and "free" = not fixed, the set
+ * T of UAVs on target t satisfies
+ *   T >= F_t;   every free u in T has allowed[u][t];   |T| <= max(capacity[t], |F_t|)  (capacity < 0 as 0)
+ * and a UAV fixed to none (its input -1, or an id that matches no tgt_id) is on no target. The three
+ * arrays are that function's (indexed by row, columns in list order, each nullable); with all three
+ * NULL this is the unconstrained problem. The feasible set is never empty (every fixed UAV on its
+ * target and every free one on none is in it).
+ * Arithmetic inside the DP is fp64, rounded in the kernel's own fixed order (not the order of J below).
+ * Tie-break: where several feasible T attain the maximum of D_{t+1}[S] in that arithmetic, the smallest
+ * T as an integer is taken; the result is then read back from t = M-1 down to 0 starting at S = all
+ * UAVs (the UAVs of T = choice_t[S] go on t, S <- S \ T). Nothing depends on timing: no atomics, every
+ * value is written by one lane in a fixed order, so two launches on the same inputs give bitwise equal
+ * outputs.
+ *  - env, env_stride, S, assignment_out, J, covered (all required): as uavhip_refine_assignments, the
+ *    same row bounds; J, covered and the ids of the result come from the code uavhip_refine_assignments
+ *    ends with, so J is bitwise uavhip_refine_assignments(assignment_out, max_sweeps = 0)'s and
+ *    comparable with every other J of this library;
+ *  - assignment_in [S][N] int32 (nullable): read only to learn where the fixed UAVs stand, converted
+ *    as uavhip_refine_assignments converts it; required when fixed != NULL;
+ *  - stats [S][2] int32 (nullable): invalid input ids, fixed_conflicts (as pass 1 of
+ *    uavhip_search_assignments_constrained counts them);
+ *  - workspace: device memory, 16-byte aligned, of workspace_bytes bytes, contents unspecified before
+ *    and after. One row needs uavhip_exact_workspace_bytes(N, M, 1) bytes: two tables of 2^N doubles
+ *    (D_t and D_{t+1}), the choice table [M][2^N] of uint16 and M 8-byte target masks (5 MiB + 256 B
+ *    at 16 x 32). A workspace that holds fewer than S rows is no error: the rows run in chunks that
+ *    fit, one after the other on `stream`. uavhip_exact_workspace_bytes returns -1 unless 1 <= N <= 16,
+ *    1 <= M <= 128 and rows >= 1.
+ * UAVHIP_EINVAL: N > UAVHIP_EXACT_MAX_N, the row bounds, a required output NULL, fixed without
+ * assignment_in, a workspace that is NULL, misaligned or smaller than one row's need. Per chunk: one
+ * launch that prepares the masks, M stage launches (the kernel boundary is the dependence between
+ * stages) and one that reads the result back. Asynchronous on `stream`, capturable; no allocation, no
+ * device or grid-wide synchronisation; the env and the inputs are only read. */
+#define UAVHIP_EXACT_MAX_N 16
+int64_t uavhip_exact_workspace_bytes(int32_t N, int32_t M, int32_t rows);
+int uavhip_solve_exact(const uavhip_env* env, int32_t env_stride, int32_t S, const uint8_t* allowed,
+                       const uint8_t* fixed, const int32_t* capacity, const int32_t* assignment_in,
+                       int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats, void* workspace,
+                       int64_t workspace_bytes, uavhip_stream_t stream);
+
 /* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
  * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
  * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is

@@ -22,6 +22,7 @@ SEQ_LEN = 5
 STATE_DIM = 14
 OBS_FLOATS = SEQ_LEN * STATE_DIM
 MAX_N, MAX_M, MAX_OBSTACLES = 64, 128, 8
+EXACT_MAX_N = 16  # UAVHIP_EXACT_MAX_N: the most UAVs uavhip_solve_exact takes
 ENV_ONE_PER_WAVE, ENV_OBS_F16, ENV_NO_REPLAY = 1, 2, 4  # uavhip_env.flags bits
 STEP_HOLD = 2  # UAVHIP_STEP_HOLD: the decode kernel's env-step mode (a finished env is held)
 
@@ -130,6 +131,9 @@ _SIGS = {
                                                  _vp, _vp]),
     "uavhip_search_assignments_constrained": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _i32, _vp, _vp,
                                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "uavhip_exact_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
+    "uavhip_solve_exact": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, ctypes.c_int64, _vp]),
     "uavhip_teacher_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
     "uavhip_expert_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

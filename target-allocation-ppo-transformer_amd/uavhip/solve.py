@@ -25,12 +25,16 @@ neighbourhood instead (uavhip_search_assignments): where no single move improves
 two UAVs' targets is made and the sweeps run again, at most X times. constraints = Constraints(...)
 (solve and baseline) runs that search under pairs that may not be flown, UAVs that are already committed
 and a limit on the UAVs of one target (uavhip_search_assignments_constrained); the decode ignores them.
+optimum() (N <= 16) is the yardstick's yardstick: the largest J any allocation of the scene reaches, by
+a subset DP over the UAVs (uavhip_solve_exact), under the same constraints when given.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-[--refine SWEEPS] [--exchanges X] [--baseline] prints one JSON line (mean / best J, mean covered, mean steps,
+[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] prints one JSON line (mean / best J, mean covered, mean steps,
 scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
 scenes where the policy beats the baseline; with --exchanges also mean_exchanges and, beside the plain
-mean_J_baseline, mean_J_baseline_exchange).
+mean_J_baseline, mean_J_baseline_exchange; with --optimum, which implies --baseline, also mean_J_optimal, each
+mean J's share of it (baseline_over_optimal, decoded_over_optimal, ...) and the share of scenes where the
+baseline reaches it, baseline_is_optimal).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
@@ -45,6 +49,8 @@ from . import _lib
 from .config import cfg as default_cfg
 from .policy import rowproj_buffer
 from .vec_env import SCENE_KEYS_F64, VecUAVEnv
+
+RTOL = 1e-12  # the project's bar on J: two J within RTOL max(1, |J|) are the same allocation's up to rounding
 
 
 @dataclass
@@ -291,6 +297,31 @@ class AllocationSolver:
             zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
         return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
 
+    @torch.no_grad()
+    def optimum(self, scenes=None, num_scenes=None, seed=None, constraints=None, max_workspace_bytes=1 << 30):
+        """The best allocation there is: the scenes solve() / baseline() would run (scene for scene
+        under the same `seed`), no policy launch, the maximum of J over every allocation by a subset DP
+        over the UAVs (uavhip_solve_exact; N <= 16, 3^N steps a target). Returns an Allocation whose
+        decode-only fields are zeros, as baseline's; refine_stats is [S, 2]: invalid ids, fixed conflicts.
+        constraints = Constraints(...): the maximum over the allocations baseline(constraints=) may end
+        on -- committed UAVs where they are, allowed pairs only, capacities kept."""
+        _check_constraints("optimum", constraints)
+        if self.N > _lib.EXACT_MAX_N:
+            raise ValueError(f"optimum: N={self.N} > {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
+        scenes, S, seed = self._scene_args("optimum", scenes, num_scenes, seed)
+        K = self.K
+        allowed = capacity = fixed_ids = None
+        if constraints is not None:
+            allowed, capacity, fixed_ids = constraints.on("optimum", S, self.N, self.M, self.device)
+        with torch.cuda.device(self.device):
+            env = self._scene_env(scenes, S, seed)
+            start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
+            assignment, J, covered, stats = env.exact_assignments(start, allowed, fixed, capacity, stride=K, rows=S,
+                                                                  max_workspace_bytes=max_workspace_bytes)
+            zi = torch.zeros(S, dtype=torch.int32, device=env.device)
+            zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
+        return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
+
 
 def main(argv=None):
     import argparse
@@ -314,9 +345,14 @@ def main(argv=None):
     ap.add_argument("--baseline", action="store_true",
                     help="also run the non-learned baseline (the local search from the empty assignment) on the "
                          "same scenes and report the share of scenes where the policy's J is larger")
+    ap.add_argument("--optimum", action="store_true",
+                    help="also the optimum of J on the same scenes (a subset DP over the UAVs, --uavs <= 16) and every "
+                         "mean J's share of it; implies --baseline")
     a = ap.parse_args(argv)
     if a.exchanges < 0:
         ap.error("--exchanges must be >= 0")
+    if a.optimum and a.uavs > _lib.EXACT_MAX_N:
+        ap.error(f"--optimum needs --uavs <= {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
     if not torch.cuda.is_available():
         raise RuntimeError("uavhip.solve decodes on the GPU (HIP) only")
     dev = torch.device("cuda:0")
@@ -339,12 +375,26 @@ def main(argv=None):
         out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
         if a.exchanges > 0:
             out.update(mean_exchanges=float(r.refine_stats[:, 4].double().mean()))
-    if a.baseline:
+    if a.baseline or a.optimum:
         b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
         out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
         if a.exchanges > 0:
             bx = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges).cpu()
             out.update(mean_J_baseline_exchange=float(bx.J.mean()))
+    if a.optimum:
+        o = solver.optimum(num_scenes=a.scenes, seed=a.seed).cpu()
+        best = float(o.J.mean())
+
+        def reaches(x):
+            return float((x.J >= o.J - RTOL * o.J.abs().clamp(min=1.0)).double().mean())
+        out.update(mean_J_optimal=best, baseline_over_optimal=float(b.J.mean()) / best)
+        if a.refine > 0:
+            out.update(decoded_over_optimal=float(r.decoded_J.mean()) / best, refined_over_optimal=float(r.J.mean()) / best)
+        else:
+            out.update(decoded_over_optimal=float(r.J.mean()) / best)
+        out.update(baseline_is_optimal=reaches(b))
+        if a.exchanges > 0:
+            out.update(baseline_exchange_over_optimal=float(bx.J.mean()) / best, baseline_exchange_is_optimal=reaches(bx))
     print(json.dumps(out))
 
 

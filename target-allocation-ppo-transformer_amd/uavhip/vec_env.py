@@ -312,6 +312,40 @@ class VecUAVEnv:
               "uavhip_search_assignments_constrained")
         return out, J, covered, stats
 
+    def exact_assignments(self, assignment=None, allowed=None, fixed=None, capacity=None, stride=1, rows=None, out=None,
+                          J=None, covered=None, stats=None, max_workspace_bytes=1 << 30):
+        """uavhip_solve_exact: the optimum of J(X) by a subset DP over the UAVs, N <= 16 (3^N steps a
+        target; include/uavhip.h has the rule and the tie-break). Rows, stride and the three constraint
+        arrays are search_assignments_constrained's, and the feasible set is its guarantee: a fixed UAV
+        stays where `assignment` puts it (it is read for nothing else, and required with `fixed`), a
+        free UAV takes allowed pairs only, no target holds more than max(capacity, its fixed UAVs).
+        The workspace (5 MiB a row at 16 x 32) is allocated for min(rows, what fits in
+        max_workspace_bytes) rows; more rows run in chunks, one after the other.
+        Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32, stats
+        [rows, 2] int32: invalid input ids, conflicts of the fixed UAVs with allowed / capacity). J is
+        refine_assignments(assignment, max_sweeps=0)'s, bitwise. The env is only read."""
+        stride = int(stride)
+        S = _rows_args("exact_assignments", self.E, stride, rows)
+        if self.N > _lib.EXACT_MAX_N:
+            raise ValueError(f"exact_assignments: N={self.N} > {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
+        if fixed is not None and assignment is None:
+            raise ValueError("exact_assignments: fixed needs assignment (a fixed UAV keeps the target it gives)")
+        check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
+        out, J, covered, stats = _rows_bufs(S, self.N, 2, self.device, assignment, out, J, covered, stats)
+        row = int(LIB.uavhip_exact_workspace_bytes(self.N, self.M, 1))
+        fit = int(max_workspace_bytes) // row
+        if fit < 1:
+            raise ValueError(f"exact_assignments: max_workspace_bytes={max_workspace_bytes} holds no row "
+                             f"(one row of {self.N} x {self.M} needs {row} bytes)")
+        nbytes = row * min(S, fit)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(LIB.uavhip_solve_exact(self.desc, stride, S, ptr(allowed), ptr(fixed), ptr(capacity), ptr(assignment),
+                                     ptr(out), ptr(J), ptr(covered), ptr(stats), ptr(workspace), nbytes,
+                                     stream_handle()), "uavhip_solve_exact")
+        return out, J, covered, stats
+
     def teacher_steps(self, assignment, n_max=None, obs=None, actions=None, reward=None, done=None, info=None,
                       steps=None, finished=None, ep_return=None, stats=None, want_info=False):
         """uavhip_teacher_steps: walk every env from its current state (reset it first) along
