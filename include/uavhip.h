@@ -582,6 +582,55 @@ int uavhip_solve_exact(const uavhip_env* env, int32_t env_stride, int32_t S, con
                        int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats, void* workspace,
                        int64_t workspace_bytes, uavhip_stream_t stream);
 
+/* Multi-start search (k_search_multistart / k_multistart_select, search_multistart.hip): per row the
+ * best of R independent runs ("replicas") of uavhip_search_assignments_constrained's rule, replica 0
+ * from assignment_in and the others from random full assignments. A local search stops at the first
+ * local optimum it meets; restarts are the simplest way past it and parallelise over replicas. Rows,
+ * env_stride, allowed [S][N][M], fixed [S][N], capacity [S][M] and assignment_in [S][N] are exactly
+ * uavhip_search_assignments_constrained's, each nullable (NULL constrains nothing; a NULL start is
+ * the empty assignment).
+ *   REPLICA r of row s, 0 <= r < R: that function's whole rule -- conversion, the two start passes,
+ *     the phases, the scans and the exchanges, with the caps max_exchanges and max_sweeps PER REPLICA
+ *     -- from start_r:
+ *       start_0 = assignment_in[s], so replica 0 is that function's result bit for bit;
+ *       r >= 1: assignment_in[s] is converted as ever (stats column 3, the invalid ids, is therefore
+ *         the same in every replica). A UAV u with fixed[s][u] != 0 keeps what the conversion gave
+ *         it. Every other UAV starts on the target of LIST index
+ *             t = (x * M) >> 32                                   (a 64-bit product, 0 <= t < M)
+ *         with x = word (u & 3) of
+ *             philox4x32_10(counter = {u >> 2, r, s, 0x5354524D}, key = {(uint32_t)seed, (uint32_t)(seed >> 32)})
+ *         -- the Philox4x32-10 of Salmon et al. (multipliers D2511F53 / CD9E8D57, key increments
+ *         9E3779B9 / BB67AE85, ten rounds; words in the order of the reference implementation's
+ *         output). A random start is a list index and needs no id conversion; what the constraints
+ *         do not admit is dropped by the rule's own pass 2.
+ *   CHOICE: with J_r the double the rule's scoring forms for replica r (the J of
+ *     uavhip_refine_assignments), r* = the lowest r among the replicas whose J_r is the largest;
+ *     "largest" and "equal" compare the doubles themselves.
+ *  - R: 1 <= R <= UAVHIP_MULTISTART_MAX_R, and S * R <= 2^30; seed: the Philox key;
+ *  - env, env_stride, S, max_exchanges, max_sweeps, assignment_in (nullable), assignment_out (required;
+ *    may alias assignment_in), J, covered (required): as uavhip_search_assignments_constrained, the same
+ *    bounds; they hold replica r*'s results, so J[s] >= that function's J[s] in every row;
+ *  - stats [S][10] int32 (nullable): columns 0-7 replica r*'s eight counters of the constrained search,
+ *    column 8 r*, column 9 the number of replicas whose J is strictly greater than replica 0's;
+ *  - J_all [S][R] f64 (nullable): J_r of every replica;
+ *  - workspace: device memory, 16-byte aligned, of at least uavhip_multistart_workspace_bytes(S, R, N)
+ *    bytes (44 + 4 N bytes per replica: J, covered, N ids, eight counters), contents unspecified before
+ *    and after. That function returns -1 unless 1 <= S, 1 <= R <= 1024, 1 <= N <= 64, S * R <= 2^30.
+ * Guarantees: those of uavhip_search_assignments_constrained, for every replica. Two calls with the same
+ * arguments give bitwise equal outputs: one wave per replica, every value written by one lane.
+ * UAVHIP_EINVAL: the row bounds, a cap < 0, R out of range, a required output NULL, a workspace that is
+ * NULL, misaligned or too small. Two launches -- S * R waves of the search, one per (row, replica), then
+ * one wave per row that chooses -- asynchronous on `stream`, capturable; the full N <= 64, M <= 128
+ * range; no allocation, no atomics, no device or grid-wide synchronisation; the env's state and scene
+ * and the inputs are only read. */
+#define UAVHIP_MULTISTART_MAX_R 1024
+int64_t uavhip_multistart_workspace_bytes(int32_t S, int32_t R, int32_t N);
+int uavhip_search_multistart(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t R, uint64_t seed,
+                             int32_t max_exchanges, int32_t max_sweeps, const uint8_t* allowed,
+                             const uint8_t* fixed, const int32_t* capacity, const int32_t* assignment_in,
+                             int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats, double* J_all,
+                             void* workspace, int64_t workspace_bytes, uavhip_stream_t stream);
+
 /* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
  * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
  * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is

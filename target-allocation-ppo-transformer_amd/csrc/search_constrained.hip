@@ -11,67 +11,14 @@
 //           N byte rows, each a coalesced load of M bytes; cap = capacity[t];
 //   fixed:  a ballot of the lanes' fixed flags, wave-uniform.
 // The sweep's candidate test is a bit test and cnt < cap on the counts build_q forms anyway; a fixed
-// UAV is a uniform skip in the sweep and in the scan. This file holds the start of the rule: the two
-// passes that drop what the constraints do not admit. No LDS, no atomics; the env is only read.
+// UAV is a uniform skip in the sweep and in the scan. The start of the rule (start_limits: the two
+// passes that drop what the constraints do not admit) is in search_device.hpp and the loop of phases and
+// exchanges in search_loop_body.hpp, where k_search_multistart shares them. No LDS, no atomics; the env
+// is only read.
 #include "search_device.hpp"
 
 namespace uavhip {
 namespace {
-
-// RowLimits from the row's arrays (a NULL array constrains nothing), then the start of the rule on
-// r.a: pass 1 counts the fixed UAVs on their targets and their conflicts, pass 2 visits the free
-// ones in ascending u and drops a pair that is not allowed or whose target is full so far.
-template <int TPL, int NR>
-__device__ __forceinline__ void start_limits(RefineRow<TPL, NR, true>& r, int s, const uint8_t* __restrict__ allowed,
-                                             const uint8_t* __restrict__ fixed, const int* __restrict__ capacity,
-                                             int& dropped, int& conflicts) {
-    const int N = r.N, M = r.M, lane = r.lane;
-    int cnt[TPL];
-#pragma unroll
-    for (int j = 0; j < TPL; ++j) {
-        const int t = lane + kWave * j;
-        unsigned long long ok = ~0ull;
-        if (allowed) {
-            ok = 0;
-            const uint8_t* row = allowed + (long long)s * N * M;
-            for (int u = 0; u < N; ++u)
-                if (t < M && row[u * M + t]) ok |= 1ull << u;
-        }
-        r.lim.ok[j] = ok;
-        int cap = 0x7fffffff;
-        if (capacity && t < M) cap = capacity[(long long)s * M + t];
-        r.lim.cap[j] = cap < 0 ? 0 : cap;
-        cnt[j] = 0;
-    }
-    r.lim.fixed = ballot(fixed && r.isu && fixed[(long long)s * N + lane]);
-
-    dropped = 0;
-    conflicts = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int u = 0; u < N; ++u) {
-            if ((int)(r.lim.fixed >> u & 1) == pass) continue;  // pass 0: the fixed UAVs; pass 1: the free ones
-            const int au = readlane_i(r.a, u);
-            if (au < 0) continue;
-            unsigned long long pair = 0, room = 0;  // nonzero: u may take au; au has room so far
-#pragma unroll
-            for (int j = 0; j < TPL; ++j) {
-                const bool mine = lane + kWave * j == au;
-                pair |= ballot(mine && (r.lim.ok[j] >> u & 1));
-                room |= ballot(mine && cnt[j] < r.lim.cap[j]);
-            }
-            if (pass == 0) {
-                conflicts += (pair == 0) + (room == 0);
-            } else if (pair == 0 || room == 0) {
-                if (lane == u) r.a = -1;
-                ++dropped;
-                continue;
-            }
-#pragma unroll
-            for (int j = 0; j < TPL; ++j)
-                if (lane + kWave * j == au) ++cnt[j];
-        }
-    }
-}
 
 template <int TPL, int NR>
 __global__ __launch_bounds__(64 * kRefineWaves) void k_search_constrained(
@@ -86,34 +33,11 @@ __global__ __launch_bounds__(64 * kRefineWaves) void k_search_constrained(
     int dropped, conflicts;
     start_limits(r, s, allowed, fixed, capacity, dropped, conflicts);
     r.load_columns();
-    int exchanges = 0, scan_clean = 0;
-    for (;;) {
-        r.phase(max_sweeps);
-        if (max_exchanges == 0) break;
-        double bd;
-        int bi, bj;
-        best_exchange(r, bd, bi, bj);
-        if (!(bd > 0.0)) {
-            scan_clean = 1;
-            break;
-        }
-        if (exchanges == max_exchanges) break;
-        const int ai = readlane_i(r.a, bi), aj = readlane_i(r.a, bj);
-        if (lane == bi) r.a = aj;
-        if (lane == bj) r.a = ai;
-        ++exchanges;
-    }
+#include "search_loop_body.hpp"
 
     r.finish(s, aout, J, covered);
     if (stats && lane < 8)
-        stats[(long long)s * 8 + lane] = lane == 0   ? r.sweeps
-                                         : lane == 1 ? r.moves
-                                         : lane == 2 ? r.converged
-                                         : lane == 3 ? r.invalid
-                                         : lane == 4 ? exchanges
-                                         : lane == 5 ? scan_clean
-                                         : lane == 6 ? dropped
-                                                     : conflicts;
+        stats[(long long)s * 8 + lane] = search_stat(r, lane, exchanges, scan_clean, dropped, conflicts);
 }
 
 }  // namespace

@@ -16,6 +16,10 @@
 // With LIM (RowLimits) a pair needs both UAVs free, j allowed on a[i] -- bit j of the mask lane a[i]
 // holds, a uniform readlane per i -- and i allowed on a[j] -- bit i of the mask of a[j], which lane j
 // fetches once per scan by a shuffle. A swap keeps every target's count: capacity is not looked at.
+//
+// Below the scan, what k_search_constrained and k_search_multistart (search_multistart.hip) share: the
+// start of the constrained rule (start_limits) and the eight counters a constrained row reports
+// (search_stat). The loop of phases, scans and exchanges they also share is search_loop_body.hpp.
 #pragma once
 #include "refine_device.hpp"
 
@@ -112,6 +116,75 @@ __device__ __forceinline__ void best_exchange(const RefineRow<TPL, NR, LIM>& r, 
     bd = readlane_d(bd, 0);
     bi = readlane_i(bi, 0);
     bj = readlane_i(bj, 0);
+}
+
+// RowLimits from the row's arrays (a NULL array constrains nothing), then the start of the rule on
+// r.a: pass 1 counts the fixed UAVs on their targets and their conflicts, pass 2 visits the free
+// ones in ascending u and drops a pair that is not allowed or whose target is full so far.
+template <int TPL, int NR>
+__device__ __forceinline__ void start_limits(RefineRow<TPL, NR, true>& r, int s, const uint8_t* __restrict__ allowed,
+                                             const uint8_t* __restrict__ fixed, const int* __restrict__ capacity,
+                                             int& dropped, int& conflicts) {
+    const int N = r.N, M = r.M, lane = r.lane;
+    int cnt[TPL];
+#pragma unroll
+    for (int j = 0; j < TPL; ++j) {
+        const int t = lane + kWave * j;
+        unsigned long long ok = ~0ull;
+        if (allowed) {
+            ok = 0;
+            const uint8_t* row = allowed + (long long)s * N * M;
+            for (int u = 0; u < N; ++u)
+                if (t < M && row[u * M + t]) ok |= 1ull << u;
+        }
+        r.lim.ok[j] = ok;
+        int cap = 0x7fffffff;
+        if (capacity && t < M) cap = capacity[(long long)s * M + t];
+        r.lim.cap[j] = cap < 0 ? 0 : cap;
+        cnt[j] = 0;
+    }
+    r.lim.fixed = ballot(fixed && r.isu && fixed[(long long)s * N + lane]);
+
+    dropped = 0;
+    conflicts = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int u = 0; u < N; ++u) {
+            if ((int)(r.lim.fixed >> u & 1) == pass) continue;  // pass 0: the fixed UAVs; pass 1: the free ones
+            const int au = readlane_i(r.a, u);
+            if (au < 0) continue;
+            unsigned long long pair = 0, room = 0;  // nonzero: u may take au; au has room so far
+#pragma unroll
+            for (int j = 0; j < TPL; ++j) {
+                const bool mine = lane + kWave * j == au;
+                pair |= ballot(mine && (r.lim.ok[j] >> u & 1));
+                room |= ballot(mine && cnt[j] < r.lim.cap[j]);
+            }
+            if (pass == 0) {
+                conflicts += (pair == 0) + (room == 0);
+            } else if (pair == 0 || room == 0) {
+                if (lane == u) r.a = -1;
+                ++dropped;
+                continue;
+            }
+#pragma unroll
+            for (int j = 0; j < TPL; ++j)
+                if (lane + kWave * j == au) ++cnt[j];
+        }
+    }
+}
+
+// column `lane` < 8 of a constrained row's stats
+template <int TPL, int NR, bool LIM>
+__device__ __forceinline__ int search_stat(const RefineRow<TPL, NR, LIM>& r, int lane, int exchanges, int scan_clean,
+                                           int dropped, int conflicts) {
+    return lane == 0   ? r.sweeps
+           : lane == 1 ? r.moves
+           : lane == 2 ? r.converged
+           : lane == 3 ? r.invalid
+           : lane == 4 ? exchanges
+           : lane == 5 ? scan_clean
+           : lane == 6 ? dropped
+                       : conflicts;
 }
 
 }  // namespace uavhip

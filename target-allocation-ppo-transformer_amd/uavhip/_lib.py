@@ -23,6 +23,7 @@ STATE_DIM = 14
 OBS_FLOATS = SEQ_LEN * STATE_DIM
 MAX_N, MAX_M, MAX_OBSTACLES = 64, 128, 8
 EXACT_MAX_N = 16  # UAVHIP_EXACT_MAX_N: the most UAVs uavhip_solve_exact takes
+MULTISTART_MAX_R = 1024  # UAVHIP_MULTISTART_MAX_R: the most replicas a row of uavhip_search_multistart runs
 ENV_ONE_PER_WAVE, ENV_OBS_F16, ENV_NO_REPLAY = 1, 2, 4  # uavhip_env.flags bits
 STEP_HOLD = 2  # UAVHIP_STEP_HOLD: the decode kernel's env-step mode (a finished env is held)
 
@@ -134,6 +135,9 @@ _SIGS = {
     "uavhip_exact_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
     "uavhip_solve_exact": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, ctypes.c_int64, _vp]),
+    "uavhip_multistart_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
+    "uavhip_search_multistart": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, ctypes.c_uint64, _i32, _i32,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp]),
     "uavhip_teacher_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
     "uavhip_expert_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

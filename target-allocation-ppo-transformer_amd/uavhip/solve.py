@@ -27,14 +27,19 @@ two UAVs' targets is made and the sweeps run again, at most X times. constraints
 and a limit on the UAVs of one target (uavhip_search_assignments_constrained); the decode ignores them.
 optimum() (N <= 16) is the yardstick's yardstick: the largest J any allocation of the scene reaches, by
 a subset DP over the UAVs (uavhip_solve_exact), under the same constraints when given.
+restarts = R > 0 (solve and baseline) runs the constrained search R times per scene in one launch
+(uavhip_search_multistart): replica 0 is what the call does without it, the others start from random
+full assignments, and the best J wins -- a near-optimal allocator at every size, constraints included.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] prints one JSON line (mean / best J, mean covered, mean steps,
+[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] [--restarts R] prints one JSON line (mean / best J, mean covered, mean steps,
 scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
 scenes where the policy beats the baseline; with --exchanges also mean_exchanges and, beside the plain
 mean_J_baseline, mean_J_baseline_exchange; with --optimum, which implies --baseline, also mean_J_optimal, each
 mean J's share of it (baseline_over_optimal, decoded_over_optimal, ...) and the share of scenes where the
-baseline reaches it, baseline_is_optimal).
+baseline reaches it, baseline_is_optimal; with --restarts R also mean_J_multistart, the baseline with R
+restarts and --exchanges' cap (32 when that is 0), and with --optimum multistart_over_optimal and
+multistart_is_optimal).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
@@ -67,6 +72,7 @@ class Allocation:
     refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
     #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean;
     #                                              [S, 8] with constraints: + pairs dropped, fixed conflicts
+    #                                              [S, 10] with restarts > 0: + the chosen replica, replicas above replica 0
 
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
@@ -205,7 +211,7 @@ class AllocationSolver:
 
     @torch.no_grad()
     def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0,
-              constraints=None):
+              constraints=None, restarts=0):
         """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
         `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
         greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
@@ -223,8 +229,18 @@ class AllocationSolver:
         every committed UAV (fixed_ids != -2) with its fixed id and polishes with
         uavhip_search_assignments_constrained (at most X exchanges, X = 0 included), which drops what the
         constraints do not admit and searches within them; refine_stats is its [S, 8] counters and
-        decoded_J stays the unconstrained decode's J. constraints = None changes no launch and no result."""
-        refine, exchanges = int(refine), int(exchanges)
+        decoded_J stays the unconstrained decode's J. constraints = None changes no launch and no result.
+        restarts = R > 0 (needs refine > 0): the polish is uavhip_search_multistart with R replicas --
+        replica 0 the polish this call would run without it (at most X exchanges, X = 0 included, under
+        the constraints when given), replicas 1..R-1 the same search from random full assignments drawn
+        with Philox key `seed` -- and the replica with the largest J is kept; refine_stats is [S, 10]: the
+        chosen replica's eight counters, its index, the replicas above replica 0. restarts = 0 launches
+        nothing new and changes no result."""
+        refine, exchanges, restarts = int(refine), int(exchanges), int(restarts)
+        if not 0 <= restarts <= _lib.MULTISTART_MAX_R:
+            raise ValueError(f"solve: restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
+        if restarts > 0 and refine == 0:
+            raise ValueError("solve: restarts > 0 needs refine > 0 (the sweeps of every replica)")
         if refine < 0:
             raise ValueError("solve: refine must be >= 0")
         if exchanges < 0:
@@ -236,6 +252,7 @@ class AllocationSolver:
             raise ValueError("solve: constraints need refine > 0 (the decode ignores them; the search applies them)")
         scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
+        allowed = capacity = fixed_ids = None
         if constraints is not None:
             allowed, capacity, fixed_ids = constraints.on("solve", S, self.N, self.M, self.device)
         with torch.cuda.device(self.device):
@@ -254,7 +271,12 @@ class AllocationSolver:
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
             if refine == 0:
                 return Allocation(assignment, J, covered, best, steps, replica_J, actions)
-            if constraints is not None:
+            if restarts > 0:
+                start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
+                refined, rJ, rcov, stats = env.search_assignments_multistart(
+                    start, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
+                    max_exchanges=exchanges, max_sweeps=refine)
+            elif constraints is not None:
                 start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
                 refined, rJ, rcov, stats = env.search_assignments_constrained(
                     start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=refine)
@@ -266,25 +288,37 @@ class AllocationSolver:
         return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats)
 
     @torch.no_grad()
-    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0, constraints=None):
+    def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0, constraints=None,
+                 restarts=0):
         """The non-learned yardstick for the same objective: the scenes solve() would run (scene for
         scene under the same `seed`), no policy launch, the best-response local search started from
         the empty assignment (a greedy constructor plus local search). Returns an Allocation whose
         decode-only fields (best_replica, steps, replica_J) are zeros. exchanges = X > 0: the search
         with at most X pairwise exchanges (uavhip_search_assignments), refine_stats [S, 6].
         constraints = Constraints(...): uavhip_search_assignments_constrained from the assignment that
-        holds the committed UAVs' fixed ids and nothing else, refine_stats [S, 8]."""
-        exchanges = int(exchanges)
+        holds the committed UAVs' fixed ids and nothing else, refine_stats [S, 8].
+        restarts = R > 0: uavhip_search_multistart with R replicas -- replica 0 the search this call would
+        run without it, the others from random full assignments drawn with Philox key `seed` -- and the
+        best J per scene, refine_stats [S, 10]. restarts = 0 launches nothing new and changes no result."""
+        exchanges, restarts = int(exchanges), int(restarts)
         if exchanges < 0:
             raise ValueError("baseline: exchanges must be >= 0")
+        if not 0 <= restarts <= _lib.MULTISTART_MAX_R:
+            raise ValueError(f"baseline: restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
         _check_constraints("baseline", constraints)
         scenes, S, seed = self._scene_args("baseline", scenes, num_scenes, seed)
         K = self.K
+        allowed = capacity = fixed_ids = None
         if constraints is not None:
             allowed, capacity, fixed_ids = constraints.on("baseline", S, self.N, self.M, self.device)
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
-            if constraints is not None:
+            if restarts > 0:
+                start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
+                assignment, J, covered, stats = env.search_assignments_multistart(
+                    start, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
+                    max_exchanges=exchanges, max_sweeps=max_sweeps)
+            elif constraints is not None:
                 start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
                 assignment, J, covered, stats = env.search_assignments_constrained(
                     start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=max_sweeps)
@@ -348,9 +382,14 @@ def main(argv=None):
     ap.add_argument("--optimum", action="store_true",
                     help="also the optimum of J on the same scenes (a subset DP over the UAVs, --uavs <= 16) and every "
                          "mean J's share of it; implies --baseline")
+    ap.add_argument("--restarts", type=int, default=0, metavar="R",
+                    help="also the baseline as the best of R restarts of the exchange search (uavhip_search_multistart; "
+                         "--exchanges' cap, or 32 when that is 0): mean_J_multistart; implies --baseline")
     a = ap.parse_args(argv)
     if a.exchanges < 0:
         ap.error("--exchanges must be >= 0")
+    if not 0 <= a.restarts <= _lib.MULTISTART_MAX_R:
+        ap.error(f"--restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
     if a.optimum and a.uavs > _lib.EXACT_MAX_N:
         ap.error(f"--optimum needs --uavs <= {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
     if not torch.cuda.is_available():
@@ -375,12 +414,15 @@ def main(argv=None):
         out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
         if a.exchanges > 0:
             out.update(mean_exchanges=float(r.refine_stats[:, 4].double().mean()))
-    if a.baseline or a.optimum:
+    if a.baseline or a.optimum or a.restarts > 0:
         b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
         out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
         if a.exchanges > 0:
             bx = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges).cpu()
             out.update(mean_J_baseline_exchange=float(bx.J.mean()))
+        if a.restarts > 0:
+            bm = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges or 32, restarts=a.restarts).cpu()
+            out.update(mean_J_multistart=float(bm.J.mean()))
     if a.optimum:
         o = solver.optimum(num_scenes=a.scenes, seed=a.seed).cpu()
         best = float(o.J.mean())
@@ -395,6 +437,8 @@ def main(argv=None):
         out.update(baseline_is_optimal=reaches(b))
         if a.exchanges > 0:
             out.update(baseline_exchange_over_optimal=float(bx.J.mean()) / best, baseline_exchange_is_optimal=reaches(bx))
+        if a.restarts > 0:
+            out.update(multistart_over_optimal=float(bm.J.mean()) / best, multistart_is_optimal=reaches(bm))
     print(json.dumps(out))
 
 

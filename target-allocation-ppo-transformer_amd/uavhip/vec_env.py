@@ -346,6 +346,46 @@ class VecUAVEnv:
                                      stream_handle()), "uavhip_solve_exact")
         return out, J, covered, stats
 
+    def search_assignments_multistart(self, assignment=None, allowed=None, fixed=None, capacity=None, restarts=16,
+                                      seed=0, stride=1, rows=None, max_exchanges=32, max_sweeps=32, out=None, J=None,
+                                      covered=None, stats=None, J_all=None):
+        """uavhip_search_multistart: per row the best of `restarts` = R independent runs (replicas) of
+        search_assignments_constrained -- replica 0 from `assignment` (its result bit for bit), the
+        others from uniform random full assignments drawn with Philox key `seed` (a fixed UAV keeps
+        the target `assignment` gives it in every replica); the caps hold per replica and the replica
+        with the largest J wins, the lowest index among equal J (include/uavhip.h has the rule). Rows,
+        stride and the three constraint arrays are search_assignments_constrained's, None included.
+        Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32, stats
+        [rows, 10] int32: the chosen replica's eight counters of the constrained search, its index,
+        the number of replicas strictly above replica 0's J). J_all [rows, R] f64, when given, receives
+        every replica's J. 1 <= R <= 1024. The workspace (44 + 4 N bytes a replica) is the env's own
+        tensor, kept and reused while it is large enough. out may be `assignment` itself. The env is
+        only read."""
+        stride, max_exchanges, max_sweeps, R = int(stride), int(max_exchanges), int(max_sweeps), int(restarts)
+        fn = "search_assignments_multistart"
+        S = _rows_args(fn, self.E, stride, rows, max_exchanges=max_exchanges, max_sweeps=max_sweeps)
+        if not 1 <= R <= _lib.MULTISTART_MAX_R:
+            raise ValueError(f"{fn}: restarts={R} must be in [1, {_lib.MULTISTART_MAX_R}]")
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{fn}: seed={seed} must be in [0, 2^64)")
+        check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
+        check_out(J_all, "J_all", torch.float64, (S, R), self.device)
+        nbytes = int(LIB.uavhip_multistart_workspace_bytes(S, R, self.N))
+        if nbytes < 0:
+            raise ValueError(f"{fn}: rows={S} x restarts={R} is more than 2^30 replicas")
+        out, J, covered, stats = _rows_bufs(S, self.N, 10, self.device, assignment, out, J, covered, stats)
+        ws = self.__dict__.get("_multistart_ws")
+        if ws is None or ws.numel() < nbytes:
+            ws = self._multistart_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(LIB.uavhip_search_multistart(self.desc, stride, S, R, seed, max_exchanges, max_sweeps, ptr(allowed),
+                                           ptr(fixed), ptr(capacity), ptr(assignment), ptr(out), ptr(J), ptr(covered),
+                                           ptr(stats), ptr(J_all), ptr(ws), ws.numel(), stream_handle()),
+              "uavhip_search_multistart")
+        return out, J, covered, stats
+
     def teacher_steps(self, assignment, n_max=None, obs=None, actions=None, reward=None, done=None, info=None,
                       steps=None, finished=None, ep_return=None, stats=None, want_info=False):
         """uavhip_teacher_steps: walk every env from its current state (reset it first) along
