@@ -107,7 +107,8 @@ enum uavhip_ist {
                                bit 1: a full reset found no fresh spare scene (state-only reset done) */
     UAVHIP_IST_SCENE_SEL,   /* active scene buffer (0/1) when scene_buffers == 2 */
     UAVHIP_IST_SCENE_STALE, /* 1: the spare buffer still holds a used scene (uavhip_scene_refresh) */
-    UAVHIP_IST_SCENE_GEN,   /* number of on-device scenes generated for this env (Philox counter) */
+    UAVHIP_IST_SCENE_GEN,   /* number of on-device scenes generated for this env = the number of the next
+                               one (Philox counter word 2; "Scene counters" at uavhip_scene_generate) */
     UAVHIP_IST_PAD0, UAVHIP_IST_PAD1, UAVHIP_IST_PAD2,
     UAVHIP_IST_COUNT
 };
@@ -183,7 +184,42 @@ int uavhip_score_pairs(const uavhip_env* env, const uint8_t* mask, uavhip_stream
 
 /* Philox4x32-10 scene generation on device (distribution of uav_env.py:65-173, not its
  * MT19937 stream) into the ACTIVE buffer of masked envs (and the spare, when scene_buffers == 2),
- * followed by K1 for them; the counter is (env, istate[SCENE_GEN]). */
+ * followed by K1 for them; the counter is (env, istate[SCENE_GEN]).
+ *
+ * Scene counters. Scene number `gen` of env e is a function of (env->seed, env_base + e, gen) alone.
+ * Every draw is philox4x32_10(counter = {index, (uint32_t)(env->env_base + e), (uint32_t)gen, stream},
+ * key = {(uint32_t)seed, (uint32_t)(seed >> 32)}); env indices therefore alias modulo 2^32. A double in
+ * [0, 1) is u01(a, b) = (((uint64_t)a << 32 | b) >> 11) * 2^-53 of two words of one block, written
+ * u01(x, y) / u01(z, w) below. Streams (index = the UAV, target list position or obstacle;
+ * g[X] = env->gen[UAVHIP_GEN_X]):
+ *   0  UAV i:  x the type key -- UAV i is type 2 iff the rank of its key among the N keys (ties: the
+ *              lower index first) is < N / 4
+ *   1  UAV i:  pos = (g[UAV_X0] + (g[UAV_X1] - g[UAV_X0]) * u01(x, y), g[MAP_H] * u01(z, w))
+ *   2  UAV i:  speed = (type 1 ? 0.35 + (0.50 - 0.35) * u01(x, y) : 0.75 + (0.90 - 0.75) * u01(x, y))
+ *              * g[WEATHER_SPEED]; heading = (-15 + 30 * u01(z, w)) degrees; vel = (cos, sin) * speed;
+ *              load = (type 1 ? 0.95 : 1.0) * g[WEATHER_LOAD]; cost = type 1 ? 1.0 : 1.25
+ *   3  index 0: n2 = min(n_remain, 1 + (int)(u01(x, y) * n_remain)), n_remain = M - M / 2 - 1 (n2 = 0
+ *              and nothing read when n_remain = 0)
+ *   4  target t: x the id key, y the value key -- tgt_id[t] is the rank of the id key among the M keys
+ *              (ties as above); with r the rank of the value key, tgt_value[t] = 4 for r < M / 2, 6 for
+ *              the next n2 ranks, 8 for the next n_remain - n2, 16 for the last
+ *   5  target t: pos = (g[TGT_X0] + (g[TGT_X1] - g[TGT_X0]) * u01(x, y), g[MAP_H] * u01(z, w))
+ *   6  target t: vel = ((u01(x, y) - 0.5) * 0.03, (u01(z, w) - 0.5) * 0.03)
+ *   7  no-fly zone k: pos from g[NFZ_X0..X1] and g[MAP_H], as stream 5
+ *   8  interceptor k: pos from g[ICP_X0..X1] and g[MAP_H], as stream 5
+ *   9  interceptor k: speed = g[ICP_S0] + (g[ICP_S1] - g[ICP_S0]) * u01(x, y); heading = 2 pi u01(z, w)
+ *              radians; vel = (cos, sin) * speed
+ * All of it in fp64 without contraction, in the order written; cos / sin are the device library's, so
+ * the two velocity fields are reproducible to its accuracy (a few ulp), everything else bit for bit
+ * (tests/device_rng.py restates it; tests/test_gpu_device_rng.py compares).
+ *
+ * istate[SCENE_GEN] is the number of the NEXT scene to draw for the env. This call draws scene
+ * SCENE_GEN into the active buffer and adds 1; with scene_buffers == 2 it then draws the following
+ * number into the spare and adds 1 again. uavhip_scene_refresh draws scene SCENE_GEN into a stale spare
+ * and adds 1; a full reset's flip draws nothing. So, from zeroed istate and with a refresh between any
+ * two flips, the active buffer holds scene k after the env's k-th flip, the fresh spare scene k + 1, and
+ * SCENE_GEN is k + 2 (k + 1 while the spare is stale). With one buffer the j-th call on an env draws
+ * scene j - 1 and leaves SCENE_GEN = j. */
 int uavhip_scene_generate(const uavhip_env* env, const uint8_t* mask, uavhip_stream_t stream);
 
 /* Regenerate (Philox + K1) the spare scene buffer of every env whose istate[SCENE_STALE] is set,
@@ -307,7 +343,17 @@ int32_t uavhip_policy_tiling(int32_t* kcols, int32_t max_params);
  * actions_in NULL -> sample a ~ Categorical(softmax(logits)) with Philox(seed, c), counter
  * c = offset + (offset_dev ? *offset_dev : 0) + b (offset_dev: device u64, lets a captured
  * hipGraph draw fresh numbers on every replay); else evaluate the given actions. Outputs
- * (nullable): action_out [B] int8, logp [B], value [B], entropy [B], logits [B][2] (all f32). */
+ * (nullable): action_out [B] int8, logp [B], value [B], entropy [B], logits [B][2] (all f32).
+ *
+ * Sampling counter. c is a 64-bit sum (it wraps modulo 2^64). The draw of window b is word 0, r, of
+ * philox4x32_10(counter = {(uint32_t)c, (uint32_t)(c >> 32), 0x5eed, 0x9e37},
+ *               key = {(uint32_t)seed, (uint32_t)(seed >> 32)});
+ * u = (r >> 8) * 2^-24, a 24-bit uniform in [0, 1) that fp32 holds exactly; with p0 = expf(l0 - lse)
+ * the fp32 probability of action 0, a = u < p0 ? 0 : 1. A draw belongs to its counter alone, not to
+ * the workgroup or lane that makes it. The same rule holds for uavhip_policy_forward_rows,
+ * uavhip_rollout_step (b = e), uavhip_rollout_steps / _rollout_actor_steps / uavhip_decode_steps
+ * (c = offset + t * offset_stride + (offset_dev ? *offset_dev : 0) + e at step t). tests/device_rng.py
+ * restates it; tests/test_gpu_device_rng.py compares every draw of every entry point. */
 int uavhip_policy_forward(const uavhip_policy* policy, const float* states, int32_t B, const int8_t* actions_in,
                           uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int8_t* action_out,
                           float* logp, float* value, float* entropy, float* logits, uavhip_stream_t stream);
