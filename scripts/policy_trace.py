@@ -42,7 +42,11 @@ v = torch.empty(B, device="cuda")
 # stamps are those of the last group: slots 0-4 and the C0 / C1 front slots of its last window, then
 # the group's batched tail (slots 5-7 and C1's tail slots)
 VALUE = os.environ.get("VALUE", "0") == "1"
-STEPS = os.environ.get("STEPS", "0") == "1" or VALUE  # k_rollout_steps (one launch of 8 steps; last step's stamps)
+# ACTOR=1: the actor-only launch alone (k_rollout_actor_steps, 9 steps; the last step's stamps). Its pruned
+# layer runs in one pass (encoder_layer_rows ONEPASS): of the chunk slots only "A.c0 attn+sync" is stamped,
+# the time from "A.ring gemm" (new-row GEMM done, ring row stored) to the barrier behind the attention.
+ACTOR = os.environ.get("ACTOR", "0") == "1"
+STEPS = os.environ.get("STEPS", "0") == "1" or VALUE or ACTOR  # k_rollout_steps (one launch of 8 steps; last step's stamps)
 fn = _lib.LIB.uavhip_steps_trace if STEPS else _lib.LIB.uavhip_policy_trace
 fn.restype = ctypes.c_int
 fn.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -57,15 +61,17 @@ if ENV:  # the stamps of the last of 8 fused steps
     eng.start()
     tr = eng.traj
     tr.obs[0].copy_(tr.obs[8])
-    if VALUE:
-        NAMES.update({1: "v.x+mask", 2: "v.prologue", 3: "v.C1 front done", 4: "v.stash stored", 5: "v.group sync",
-                      6: "v.stash loaded", 7: "v.heads"})
+    if VALUE or ACTOR:
+        if VALUE:
+            NAMES.update({1: "v.x+mask", 2: "v.prologue", 3: "v.C1 front done", 4: "v.stash stored", 5: "v.group sync",
+                          6: "v.stash loaded", 7: "v.heads"})
         big = RolloutEngine(env, net, horizon=9, deferred_value=False)
         big.traj.obs[0].copy_(tr.obs[0])
         tr = big.traj
         net.rollout_actor_steps(env, tr.obs, big.rowproj, 0, True, tr.actions, tr.logp, tr.rewards, tr.dones, tr.info,
                                 seed=0, offset=0, offset_stride=B, offset_dev=big.counter)
-        net.value_steps(tr.obs, big.rowproj, 0, tr.values, tr.last_values)
+        if VALUE:
+            net.value_steps(tr.obs, big.rowproj, 0, tr.values, tr.last_values)
     elif STEPS:
         net.rollout_steps(env, tr.obs[:9].contiguous(), eng.rowproj, 0, True, tr.actions[:8], tr.logp[:8],
                           tr.values[:8], tr.rewards[:8], tr.dones[:8], tr.info[:8], seed=0, offset=0,

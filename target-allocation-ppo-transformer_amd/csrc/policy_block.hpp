@@ -251,7 +251,9 @@ enum { kEnvGrp = 1, kEnvWave = 2, kEnvBoth = 3 };
 // is not written.
 // AONLY (inference, ROWS, ENV): the mirror image, the actor trunk and head only and then the env step
 // (k_decode_steps) -- the critic's ring rows are neither read nor written, no value; env b decodes
-// greedily (a = l1 > l0) iff greedy_stride > 0 and b % greedy_stride == 0, else it samples.
+// greedily (a = l1 > l0) iff greedy_stride > 0 and b % greedy_stride == 0, else it samples. Its pruned
+// layer attends in the projection's registers, one wave per head (encoder_layer_rows ONEPASS): bitwise
+// the two-chunk path's outputs and ring rows.
 // ETAG: the env step's instantiation tag (envdev::step_once TAG; 1 in k_rollout_actor_steps).
 template <bool TR, bool ROWS, int ENV, bool VONLY = false, bool AONLY = false, int ETAG = 0>
 __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __restrict__ P, const float* __restrict__ states,
@@ -336,7 +338,14 @@ __device__ __forceinline__ void policy_block(TID_F Smem& sm, const float* __rest
     [[maybe_unused]] envgrp::GPending gq;
     // actor trunk (1 layer) + head
     if constexpr (ROWS) {
-        if (do_actor) {
+        if constexpr (AONLY) {  // the actor-only step: attention in the projection's registers
+            RingPre<kActorTrunk> pw[3];
+            RowPre1 rp;
+            rows_prologue_head(TID_C sm, P, pw, rp, rio, [&] { a0f_from_tmax(TID_C sm); });
+            PTR(2);
+            __syncthreads();
+            encoder_layer_rows<kActorTrunk, true>(TID_C sm, P, pw, rp, rio, b0);
+        } else if (do_actor) {
             RingPre<kActorTrunk> pw[3];
             RowPre<2> rp;
             rows_prologue<kActorTrunk>(TID_C sm, P, pw, rp, rio, b0, [&] { a0f_from_tmax(TID_C sm); });

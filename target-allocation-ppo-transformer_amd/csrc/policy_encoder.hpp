@@ -214,6 +214,12 @@ __device__ void attention_full(TID_F Smem& sm, int c, const float* __restrict__ 
 // One (query, head) task per 4 consecutive lanes, each lane owning 4 of the 16 head dims
 // (dot products reduced over the quad with two xor-shuffles). _core: one query position (nqs = 1):
 // threads < 256 own one task each, its output in `o`.
+// Two lane mappings compute this arithmetic. Here, the LDS mapping: the quad is lane bits 0-1 (lane q4
+// owns dims 4 q4 .. 4 q4 + 3), reduced with add_xor1 then add_xor2. In attention_head, the MFMA tile
+// mapping: the quad is lane bits 4-5 (lane (p, g) owns dims 4g .. 4g + 3), reduced with add_xor16 then
+// add_xor32. Either tree adds the partner across the quad's low bit first, then across its high bit:
+// (d0 + d1) + (d2 + d3) in every lane, each sum of the same two values (IEEE addition commutes), so the
+// scores -- and everything after them, which is per lane -- are bitwise equal.
 __device__ __forceinline__ void attention_task(TID_F Smem& sm, int task, int qs0, f32x4& o, int& ti, int& d0) {
     const int q4 = TIDX() & 3;
     const int hh = task & 3, rest = task >> 2, p = rest & 15, si = qs0 + (rest >> 4);
@@ -245,6 +251,43 @@ __device__ __forceinline__ void attention_task(TID_F Smem& sm, int task, int qs0
 }
 __device__ __forceinline__ void attention_out(TID_F Smem& sm, int c, int ti, int d0, const f32x4 o, float sc) {
     hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw(ti, 4 * c * HD + d0), o * sc);
+}
+// attention_task for ONE head with the operands already in registers, in the lane mapping of a 16-row
+// MFMA output tile: lane (p = lane & 15, g = lane >> 4) holds dims 4g .. 4g + 3 of sample p's query, keys
+// and values (k[j], v[j]: position j), the head being the wave's. The quad of attention_task (lane bits
+// 0-1, add_xor1 then add_xor2) sits on lane bits 4-5 here (add_xor16 then add_xor32): both trees form
+// (d0 + d1) + (d2 + d3) of the four lanes' partial dots, and the two operands of every sum are the same
+// pair of values, so each score is bitwise attention_task's. Everything else is its arithmetic, lane by
+// lane. Returns the lane's four output dims (unscaled).
+// attention_weights: the first half -- e[j] = exp(score_j - max) and 1 / sum(e), the same in the four lanes
+// of a quad; att_mix with the values is the second.
+__device__ __forceinline__ float attention_weights(TID_F const Smem& sm, const f32x4 q_, const f32x4 (&k)[S],
+                                                   float (&sc)[S]) {
+    const int p = LANE() & 15;
+    const f32x4 q = q_ * kAttQ;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        float part = att_dot(q, k[j]);
+        part = add_xor32(add_xor16(part));
+        sc[j] = sm.mask[p * S + j] ? -INFINITY : part;
+        mx = j ? fmaxf(mx, sc[j]) : sc[j];
+    }
+    float den = 0.f;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        sc[j] = __expf(sc[j] - mx);
+        den = j ? den + sc[j] : sc[j];
+    }
+    return att_recip(den);
+}
+__device__ __forceinline__ f32x4 attention_head(TID_F const Smem& sm, const f32x4 q_, const f32x4 (&k)[S],
+                                                const f32x4 (&v)[S]) {
+    float sc[S];
+    const float inv = attention_weights(TID_C sm, q_, k, sc);
+    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+    att_mix(o, sc, inv, v);
+    return o;
 }
 template <int trunk, int layer>
 __device__ void attention_chunk(TID_F Smem& sm, int c, int qs0, int nqs, const float* __restrict__ P = nullptr) {
@@ -283,8 +326,10 @@ __device__ __forceinline__ EmbPre embed_load(TID_F const float* __restrict__ P) 
 }
 // MODE kEmbH: h = e + pos for all 5 positions (sm.h). kEmbSplit: also e of position 4 (no pos)
 // -> sm.ctx rows 64-79 (the window-row projection path's in_proj input). kEmbRows: only e of
-// positions 0-3 -> sm.ctx (row projection fill).
-enum { kEmbH = 0, kEmbSplit = 1, kEmbRows = 2 };
+// positions 0-3 -> sm.ctx (row projection fill). kEmbOne (the actor-only step, encoder_layer_rows
+// ONEPASS): kEmbSplit, but the planes of e of position 4 go to sm.big rows 0-15 -- its attention writes
+// sm.ctx rows 64-79 with no barrier after the new-row GEMM, whose operand must then live elsewhere.
+enum { kEmbH = 0, kEmbSplit = 1, kEmbRows = 2, kEmbOne = 3 };
 // PL (kEmbH): also the two fp16 planes of h into sm.ctx (the split layer-0 in_proj's operand,
 // encoder_layer_split).
 template <int trunk, bool TR = false, int MODE = kEmbH, bool PL = false>
@@ -293,7 +338,9 @@ __device__ void embed_apply(TID_F Smem& sm, const EmbPre& ep, float* e_out = nul
     constexpr int NT = MODE == kEmbRows ? S - 1 : S;
     // the ring forward's actor (its only layer is pruned to position 4): positions 0-3 come from the
     // ring rows and only position 4 is a residual, so only its embedding is formed
-    constexpr int CT0 = MODE == kEmbSplit && trunk == kActorTrunk ? S - 1 : 0;
+    constexpr int CT0 = (MODE == kEmbSplit || MODE == kEmbOne) && trunk == kActorTrunk ? S - 1 : 0;
+    static_assert(MODE != kEmbOne || (trunk == kActorTrunk && split_slot(layer_param(trunk, 0, INW)) >= 0),
+                  "the actor's one-pass step: a split new-row GEMM");
     f32x4 acc[NT];
 #pragma unroll
     for (int ct = CT0; ct < NT; ++ct) {
@@ -310,7 +357,9 @@ __device__ void embed_apply(TID_F Smem& sm, const EmbPre& ep, float* e_out = nul
         constexpr bool ring_planes = split_slot(layer_param(trunk, 0, INW)) >= 0;  // the ring GEMM's operand
         // the planes of layer 0's input scaled per token (its window row's range)
         const float esc = (ring_planes || PL) ? es_factor<trunk, -1>(sm, ct * SPW + i16) : 1.f;
-        if ((MODE == kEmbRows || (MODE == kEmbSplit && ct == S - 1)) && ring_planes)
+        if (MODE == kEmbOne && ct == S - 1)
+            hsplit_store(reinterpret_cast<_Float16*>(sm.big), psw(i16, 16 * wv + 4 * g), e * esc);
+        else if ((MODE == kEmbRows || (MODE == kEmbSplit && ct == S - 1)) && ring_planes)
             hsplit_store(reinterpret_cast<_Float16*>(sm.ctx), psw((ct * SPW + i16), 16 * wv + 4 * g), e * esc);
         else if (MODE == kEmbRows || (MODE == kEmbSplit && ct == S - 1)) *reinterpret_cast<f32x4*>(sm.ctx + o) = e;
         if (MODE == kEmbRows) continue;
@@ -565,9 +614,11 @@ __device__ __forceinline__ void layer_tail_fwd(TID_F Smem& sm, const float* __re
 //   layer 0 (training forward): in sm.ctx (the embedding wrote them beside its fp32 rows in sm.h) --
 //               so chunk 0's attention output waits in registers until chunk 1's GEMMs have read
 //               sm.ctx, then both chunks are written.
-// TAIL = false (k_value_steps): stops after the attention -- its output's planes in sm.ctx rows 64-79
-// and the residual rows still in sm.ctx rows 0-15; the caller runs the tail later (layer_tail BATCH).
-template <int trunk, int layer, bool last, bool TR, class F = NoHook, bool TAIL = true>
+// Lane mapping: the chunk's Q | K | V meet in sm.big and attention_task / attention_full_core read them
+// with 4 lanes per task (the quad on lane bits 0-1). The value pass (k_value_steps) runs the front of its
+// pruned layer 1 in the other mapping, the quad on lane bits 4-5 and no Q | K | V in sm.big
+// (encoder_front_pairs below), and the tail later (layer_tail BATCH).
+template <int trunk, int layer, bool last, bool TR, class F = NoHook>
 __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float* __restrict__ P, HPre<2> pkv,
                                                     const TrainLayerIO& io, int b0, F pre_ln2) {
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1 + layer);  // trace slot base
@@ -612,7 +663,7 @@ __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float*
                     (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, qtok0 + 16 * ct + i16) + bq;
         }
         if (c == 0) pkv = hprefetch<2>(TID_C P, si, D, kv_row(wv, 1), 0);
-        else if constexpr (TAIL) po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
+        else po = tail_prefetch<trunk, layer, last, TR>(TID_C P);
         PTR(tb + 1 + 3 * c);
         __syncthreads();
         PTR(tb + 2 + 3 * c);
@@ -646,7 +697,80 @@ __device__ __forceinline__ void encoder_layer_split(TID_F Smem& sm, const float*
         __syncthreads();
         PTR(tb + 3 + 3 * c);
     }
-    if constexpr (TAIL) layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
+    layer_tail_fwd<trunk, layer, last, TR, F>(TID_C sm, P, po, io, b0, pre_ln2);
+}
+
+// The front of a pruned encoder_layer_split -- up to the attention output's planes in sm.ctx rows 64-79,
+// the residual rows still in sm.ctx rows 0-15 -- for k_value_steps' value_front, with the chunked front's
+// own GEMMs (per chunk of 4 heads one wave of a SIMD runs the K tile of a head and its Q tile, its partner
+// the V tile; the same hgemm_tile calls per tile, so every token column's sums are unchanged) but without
+// the trip through sm.big: an accumulator tile holds dims 4g .. 4g + 3 of sample p's five keys (or
+// values) in lane (p, g), attention_head's mapping. The K wave forms the scores and the softmax weights
+// in registers (attention_weights) and hands e[0..4] and 1 / sum(e) of each (head, sample) to its SIMD
+// partner through 6 floats of sm.big; the V wave mixes its values with them (att_mix) and writes the
+// planes. The roles swap between the chunks (chunk 0: waves 0-3 K, waves 4-7 V; chunk 1 the reverse), so
+// every wave runs one K + Q + softmax and one V and mixes one chunk. Both chunks' GEMMs run back to back;
+// one barrier in front of the mix and one behind it replace the four of the chunk loop.
+// pkv: kv_prefetch's blocks (chunk 0's roles are encoder_layer_split's).
+constexpr int kAttW = 8;  // floats per (chunk, head, sample) in sm.big: e[0..4], 1 / sum(e), pad
+template <int trunk, int layer>
+__device__ __forceinline__ void encoder_front_pairs(TID_F Smem& sm, const float* __restrict__ P, HPre<2> pkv) {
+    static_assert(split_inproj<trunk, layer>(), "the input's planes in sm.h: a pruned layer after a full one");
+    constexpr int si = split_slot(layer_param(trunk, layer, INW));
+    constexpr int qtok0 = (S - 1) * SPW;
+    const float* bin = P + kOffs.o[layer_param(trunk, layer, INB)];
+    const int l = LANE(), i16 = l & 15, g = l >> 4, wv = TIDX() >> 6, h = wv & 3;
+    const _Float16* hp = reinterpret_cast<const _Float16*>(sm.h);
+    f32x4 v[S];  // the values of the chunk this wave mixes (waves 0-3: chunk 1, waves 4-7: chunk 0)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const bool kw = (wv < 4) == (c == 0);  // wave-uniform: this wave has the chunk's K, Q and softmax
+        const int row = (kw ? D : 2 * D) + 64 * c + 16 * h;
+        HPre<2> pq;
+        if (kw) pq = hprefetch<2>(TID_C P, si, D, 64 * c + 16 * h, 0);
+        f32x4 t[S];
+        {
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(bin + row + 4 * g);
+            f32x4 hi[S], lo[S];
+            zero(hi);
+            zero(lo);
+            hgemm_tile<S, 2>(TID_C hi, lo, pkv, P, si, D, row, 0, hp, 0);
+#pragma unroll
+            for (int ct = 0; ct < S; ++ct)
+                t[ct] = (hi[ct] + lo[ct] * kLoScale) * in_inv<trunk, layer>(sm, 16 * ct + i16) + bb;
+        }
+        if (kw) {
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(bin + 64 * c + 16 * h + 4 * g);
+            f32x4 hi[1], lo[1];
+            zero(hi);
+            zero(lo);
+            hgemm_tile<1, 2>(TID_C hi, lo, pq, P, si, D, 64 * c + 16 * h, 0, hp, qtok0);
+            const f32x4 q = (hi[0] + lo[0] * kLoScale) * in_inv<trunk, layer>(sm, qtok0 + i16) + bq;
+            float e[S];
+            const float inv = attention_weights(TID_C sm, q, t, e);
+            if (g == 0) {  // the four lanes of a quad hold the same values
+                float* w = sm.big + ((c * 4 + h) * SPW + i16) * kAttW;
+                *reinterpret_cast<f32x4*>(w) = f32x4{e[0], e[1], e[2], e[3]};
+                *reinterpret_cast<f32x2_t*>(w + 4) = f32x2_t{e[4], inv};
+            }
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < S; ++ct) v[ct] = t[ct];
+        }
+        if (c == 0) pkv = hprefetch<2>(TID_C P, si, D, (wv < 4 ? 2 * D : D) + 64 + 16 * h, 0);
+    }
+    __syncthreads();
+    {
+        const int c = wv < 4 ? 1 : 0;
+        const float* w = sm.big + ((c * 4 + h) * SPW + i16) * kAttW;
+        const f32x4 e4 = *reinterpret_cast<const f32x4*>(w);
+        const f32x2_t e1 = *reinterpret_cast<const f32x2_t*>(w + 4);
+        const float e[S] = {e4.x, e4.y, e4.z, e4.w, e1.x};
+        f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+        att_mix(o, e, e1.y, v);
+        attention_out(TID_C sm, c, qtok0 + i16, 16 * h + 4 * g, o, att_sc<trunk, layer>(sm, i16).sc);
+    }
+    __syncthreads();
 }
 
 // One post-LN nn.TransformerEncoderLayer (relu FFN 256, 8 heads). last: prune to column tile 4.
@@ -780,6 +904,56 @@ __device__ __forceinline__ void ring_load(TID_F RowPre<NP>& r, const Smem& sm, c
     }
 }
 
+// The actor-only step's ring operands (encoder_layer_rows ONEPASS): wave wv owns head wv, and lane
+// (p = lane & 15, g = lane >> 4) holds dims 4g .. 4g + 3 of sample p -- the lane mapping of the new-row
+// GEMM's accumulators, so the ring rows meet the new row's Q | K | V in registers.
+struct RowPre1 {
+    f32x4 v[S - 1][2];  // [position 0-3][K, V]: the lane's four dims of its sample's ring rows, as loaded
+    int ok;             // bit s: position s is a real row of an env in range (else v[s] reads as zero)
+    f32x4 pt;           // this thread's float4 of the [5][K 128 | V 128] Win pos_s table (-> sm.red)
+    f32x4 pq;           // Win pos_4 of the lane's four Q dims
+    f32x4 bias[3];      // as RowPre's
+};
+constexpr int kPpos1Vec = S * 2 * D / 4;  // float4s of the actor's K | V table: fills sm.red exactly
+static_assert(kPpos1Vec * 4 * sizeof(float) == sizeof(Smem::red) && kPpos1Vec <= NTHR, "the K | V table in sm.red");
+__device__ __forceinline__ void ppos_load_head(TID_F RowPre1& r, const RowIO& rio) {
+    const float* pp = rio.rp;  // the actor's rows of the table: [s][Q | K | V]
+    const int i = TIDX() % kPpos1Vec;  // (threads past the table reload, unused)
+    r.pt = *reinterpret_cast<const f32x4*>(pp + (i >> 6) * 3 * D + D + 4 * (i & 63));
+    r.pq = *reinterpret_cast<const f32x4*>(pp + (S - 1) * 3 * D + 16 * (TIDX() >> 6) + 4 * (LANE() >> 4));
+}
+__device__ __forceinline__ void ppos_stage_head(TID_F Smem& sm, const RowPre1& r) {
+    if (TIDX() < kPpos1Vec) reinterpret_cast<f32x4*>(sm.red)[TIDX()] = r.pt;  // [s][K 128 | V 128]
+}
+// ring_load for one head per wave: K and V of positions 0-3 of head wv, 8 float4 per lane, under
+// ring_load's rules (predicates and offsets first, then unconditional loads back to back; a masked or
+// out-of-range item reads a valid row and becomes zero). The zero is put in by the consumer (ring_value,
+// from `ok`): a select here would sit inside the new-row GEMM's k-block and make it wait for the loads.
+__device__ __forceinline__ void ring_load_head(TID_F RowPre1& r, const Smem& sm, const RowIO& rio, int b0) {
+    const float* slots = rio.rp + kPposFloats;
+    const int p = LANE() & 15, b = b0 + p;
+    const int col = 16 * (int)(TIDX() >> 6) + 4 * (LANE() >> 4);
+    int off[S - 1], m[S - 1];
+#pragma unroll
+    for (int s = 0; s < S - 1; ++s) m[s] = sm.mask[p * S + s];  // every lane, back to back: one LDS round trip
+    r.ok = 0;
+#pragma unroll
+    for (int s = 0; s < S - 1; ++s) {
+        const bool ok = (b < rio.B) & (m[s] == 0);
+        const int slot = (rio.g + 1 + s) % 5;
+        off[s] = ok ? (slot * rio.B + b) * kRowFloats + col : col;
+        r.ok |= (int)ok << s;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int s = 0; s < S - 1; ++s)
+#pragma unroll
+        for (int part = 0; part < 2; ++part) r.v[s][part] = *reinterpret_cast<const f32x4*>(slots + off[s] + part * D);
+}
+__device__ __forceinline__ f32x4 ring_value(const RowPre1& r, int s, int part) {
+    return (r.ok >> s) & 1 ? r.v[s][part] : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // acc[r] += W[row[r] + i][k] . X[xtok0 + j][k] over k in [0, 128): R weight tiles against one
 // activation tile (shared B operand), blocks < D from `pre` (D = KB: weights fully preloaded).
 // `issued()` runs right after the last weight load is issued: loads it issues queue behind the
@@ -867,10 +1041,22 @@ using RingPre = std::conditional_t<split_ring<trunk>(), HPre<2>, APre<kPwD>>;
 // 16 wv: this wave's Q, K and V features, all in chunk wv >> 2) and the ring rows of positions
 // 0-3 from `rp`; then attention and layer_tail as in encoder_layer. Expects sm.ctx rows 64-79 =
 // e of position 4 (embed_apply kEmbSplit), sm.red = Win pos_s of chunk 0 (ppos_stage).
-template <int trunk, int NP>
-__device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* __restrict__ P, const RingPre<trunk> (&pw)[3], RowPre<NP>& rp,
+// Q | K | V reach the attention in one of two lane mappings. Default: through sm.big, two chunks of 4
+// heads, each an assembly phase, a barrier, attention_chunk / attention_full (4 lanes per task, the quad
+// on lane bits 0-1) and another barrier. ONEPASS (the actor-only step, policy_block AONLY; RP = RowPre1):
+// the new-row GEMM's accumulators of wave wv are Q, K and V of head wv (HD = 16) with lane (i16, g) holding
+// dims 4g .. 4g + 3 of sample i16, so each wave attends for its own head in registers (attention_head, the
+// quad on lane bits 4-5: the same reduction tree, see attention_task) on ring rows loaded in that mapping
+// (ring_load_head) -- no assembly, no chunk loop, one barrier before the tail. It expects e of position 4
+// in sm.big rows 0-15 (embed_apply kEmbOne) and the whole K | V table of Win pos_s in sm.red
+// (rows_prologue_head). Every sum keeps its order: projection + bias, then + Win pos_s.
+template <int trunk, bool ONEPASS = false, class RP>
+__device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* __restrict__ P, const RingPre<trunk> (&pw)[3], RP& rp,
                                    const RowIO& rio, int b0) {
     constexpr bool last = trunk == kActorTrunk;  // the actor's layer 0 is its last (pruned) layer
+    constexpr int NP = row_parts<trunk>();
+    static_assert(std::is_same_v<RP, std::conditional_t<ONEPASS, RowPre1, RowPre<NP>>>, "the variant's ring operands");
+    static_assert(!ONEPASS || (last && split_ring<trunk>()), "one pass: the actor's pruned layer, split new-row GEMM");
     constexpr int P0 = 3 - NP, ROFF = trunk == kActorTrunk ? 0 : 2 * D;
     [[maybe_unused]] constexpr int tb = 8 + 16 * (trunk == 0 ? 0 : 1);
     PTR(tb);
@@ -879,14 +1065,19 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
     const int rows[3] = {16 * wv, D + 16 * wv, 2 * D + 16 * wv};
     f32x4 acc[3] = {};
     auto ring_issue = [&] {
-        ring_load<trunk>(TID_C rp, sm, rio, b0, 0);
-        if (trunk == kActorTrunk) ring_load<trunk>(TID_C rp, sm, rio, b0, 1);
+        if constexpr (ONEPASS) {
+            ring_load_head(TID_C rp, sm, rio, b0);
+        } else {
+            ring_load<trunk>(TID_C rp, sm, rio, b0, 0);
+            if (trunk == kActorTrunk) ring_load<trunk>(TID_C rp, sm, rio, b0, 1);
+        }
     };
     if constexpr (split_ring<trunk>()) {  // e of position 4 as planes in sm.ctx (embed_apply kEmbSplit)
         f32x4 lo[3] = {};
         const float inv = es_factor<trunk, 1>(sm, (S - 1) * SPW + i16);  // the new row's scale
         hgemm_rows<3, 2>(TID_C acc, lo, pw, P, split_slot(layer_param(trunk, 0, INW)), D, rows,
-                         reinterpret_cast<const _Float16*>(sm.ctx), (S - 1) * SPW, ring_issue);
+                         reinterpret_cast<const _Float16*>(ONEPASS ? sm.big : sm.ctx), ONEPASS ? 0 : (S - 1) * SPW,
+                         ring_issue);
 #pragma unroll
         for (int j = 0; j < 3; ++j) acc[j] = (acc[j] + lo[j] * kLoScale) * inv;
     } else {
@@ -894,11 +1085,48 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) acc[j] += rp.bias[j];  // u = Win e + b
+    if constexpr (!ONEPASS) {
     if (b0 + i16 < rio.B) {  // the new row -> ring slot g mod 5
         float* dst = rio.rp + kPposFloats + ((size_t)(rio.g % 5) * rio.B + b0 + i16) * kRowFloats + ROFF + 16 * wv + 4 * g;
 #pragma unroll
         for (int j = P0; j < 3; ++j) *reinterpret_cast<f32x4*>(dst + (j - P0) * D) = acc[j];
     }
+    }
+    if constexpr (ONEPASS) {
+        // One pass, one wave per head: wave wv's accumulators are Q, K and V of head wv for the 16
+        // samples, lane (i16, g) holding dims 4g .. 4g + 3 of sample i16 -- attention_head's mapping, and
+        // ring_load_head's. Nothing goes through sm.big and no barrier separates projection and attention;
+        // the one below lets the tail's out-projection read every head's planes.
+        PTR(tb + 13);
+        const TailPre po = tail_prefetch<trunk, 0, last, false>(TID_C P);
+        const float* pl = reinterpret_cast<const float*>(sm.red) + 16 * wv + 4 * g;  // [s][K 128 | V 128]
+        f32x4 k[S], v[S];
+#pragma unroll
+        for (int s = 0; s < S - 1; ++s) {
+            k[s] = ring_value(rp, s, 0);
+            v[s] = ring_value(rp, s, 1);
+        }
+        k[S - 1] = acc[1];
+        v[S - 1] = acc[2];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {  // projection + bias first, then + Win pos_s
+            k[s] += *reinterpret_cast<const f32x4*>(pl + s * 2 * D);
+            v[s] += *reinterpret_cast<const f32x4*>(pl + s * 2 * D + D);
+        }
+        const f32x4 o = attention_head(TID_C sm, acc[0] + rp.pq, k, v);
+        attention_out(TID_C sm, 0, (S - 1) * SPW + i16, 16 * wv + 4 * g, o, att_sc<trunk, 0>(sm, i16).sc);
+        // The new row -> ring slot g mod 5, behind the attention (no load of this step reads that slot):
+        // under its branch the compiler's vmcnt bookkeeping waits for everything outstanding at the next
+        // use of a load -- in front of the attention that was the store's round trip on top of the loads'.
+        if (b0 + i16 < rio.B) {
+            float* dst = rio.rp + kPposFloats + ((size_t)(rio.g % 5) * rio.B + b0 + i16) * kRowFloats + 16 * wv + 4 * g;
+            *reinterpret_cast<f32x4*>(dst) = acc[1];
+            *reinterpret_cast<f32x4*>(dst + D) = acc[2];
+        }
+        __syncthreads();
+        PTR(tb + 3);  // "attn+sync"; the other chunk-phase slots (tb + 1 .. tb + 6) are not stamped
+        layer_tail_fwd<trunk, 0, last, false>(TID_C sm, P, po, TrainLayerIO{}, b0);
+    } else {
     if (trunk != kActorTrunk) ring_load<trunk>(TID_C rp, sm, rio, b0, 1);
     PTR(tb + 13);
     const float* pl = reinterpret_cast<const float*>(sm.red);
@@ -934,6 +1162,7 @@ __device__ __forceinline__ void encoder_layer_rows(TID_F Smem& sm, const float* 
         PTR(tb + 3 + 3 * c);
     }
     layer_tail_fwd<trunk, 0, last, false>(TID_C sm, P, po, TrainLayerIO{}, b0);
+    }
 }
 
 // Everything layer 0 of a trunk needs before its new-row GEMM (which then issues the ring loads
@@ -958,6 +1187,26 @@ __device__ __forceinline__ void rows_prologue(TID_F Smem& sm, const float* __res
     hook();  // behind the loads above: its latency overlaps theirs
     embed_apply<trunk, false, kEmbSplit>(TID_C sm, ep);
     ppos_stage(TID_C sm, rp, 0);
+}
+// rows_prologue of the actor-only step (encoder_layer_rows ONEPASS): the whole K | V table of Win pos_s
+// goes to sm.red at once, the Q row of position 4 stays in registers, and the embedding's planes go to
+// sm.big (embed_apply kEmbOne).
+template <class H = NoHook>
+__device__ __forceinline__ void rows_prologue_head(TID_F Smem& sm, const float* __restrict__ P,
+                                                   RingPre<kActorTrunk> (&pw)[3], RowPre1& rp, const RowIO& rio,
+                                                   H hook = H{}) {
+    constexpr int trunk = kActorTrunk;
+    const int wv = TIDX() >> 6;
+    const EmbPre ep = embed_load<trunk>(TID_C P);
+    ppos_load_head(TID_C rp, rio);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pw[j] = hprefetch<2>(TID_C P, split_slot(layer_param(trunk, 0, INW)), D, j * D + 16 * wv, 0);
+    const float* bin = P + kOffs.o[layer_param(trunk, 0, INB)];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) rp.bias[j] = *reinterpret_cast<const f32x4*>(bin + j * D + 16 * wv + 4 * (LANE() >> 4));
+    hook();  // behind the loads above: its latency overlaps theirs
+    embed_apply<trunk, false, kEmbOne>(TID_C sm, ep);
+    ppos_stage_head(TID_C sm, rp);
 }
 
 }  // namespace pol

@@ -229,9 +229,10 @@ __device__ __forceinline__ void value_front(TID_F Smem& sm, const float* __restr
         __syncthreads();
         encoder_layer_rows<kCriticTrunk>(TID_C sm, P, pw, rp, rio, b0);
     }
+    // layer 1's front: the chunked GEMMs, the last token's attention in their registers
     const KvPre<kCriticTrunk, 1, false> pkv = kv_prefetch<kCriticTrunk, 1, false>(TID_C P);
     __syncthreads();
-    encoder_layer_split<kCriticTrunk, 1, true, false, NoHook, false>(TID_C sm, P, pkv, TrainLayerIO{}, b0, NoHook{});
+    encoder_front_pairs<kCriticTrunk, 1>(TID_C sm, P, pkv);
     // the attention output's planes (sm.ctx rows 64-79) and the residual rows (sm.ctx rows 0-15, fp32)
     PTR(3);
     const f32x4* cx = reinterpret_cast<const f32x4*>(sm.ctx);
