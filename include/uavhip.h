@@ -677,6 +677,50 @@ int uavhip_search_multistart(const uavhip_env* env, int32_t env_stride, int32_t 
                              int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats, double* J_all,
                              void* workspace, int64_t workspace_bytes, uavhip_stream_t stream);
 
+/* Multi-start search from GIVEN starts (the same two kernels): uavhip_search_multistart with the first R0
+ * of a row's R replicas started from R0 assignments of the caller's -- the K decoded replicas of a
+ * policy, say -- and the other R - R0 from random full assignments as ever. Everything not named here is
+ * uavhip_search_multistart's: rows, env_stride, allowed [S][N][M], fixed [S][N], capacity [S][M] (each
+ * nullable), the caps per replica, CHOICE, stats [S][10], J_all [S][R], the workspace and
+ * uavhip_multistart_workspace_bytes(S, R, N).
+ *   starts [S][R0][N] int32: target ids or -1, R0 starts per row, start k of row s at starts[(s * R0 + k) * N].
+ *   FIXED0: for a row s, fixed0[u] = the list index starts[s][0][u] converts to (-1 for -1 and for an id
+ *     that matches no tgt_id), for the UAVs u with fixed[s][u] != 0. EVERY replica of the row holds those
+ *     UAVs there, so all replicas of a row solve the same constrained problem and their J are comparable;
+ *     what starts[s][r][u], r >= 1, says of a fixed u is not read.
+ *   GIVEN REPLICA r, 0 <= r < R0:
+ *       start_r[u] = fixed0[u] for a fixed u, else starts[s][r][u] converted;
+ *     the conversion is uavhip_refine_assignments' own (of a duplicated id the lowest list index; an id
+ *     that matches no tgt_id counts as -1 and is counted). From start_r the replica is
+ *     uavhip_search_assignments_constrained's whole rule -- the two start passes, the phases, the scans
+ *     and the exchanges -- bit for bit that function's result for assignment_in = start r with row 0's
+ *     ids written over the fixed UAVs. stats column 3 of a given replica counts the invalid ids of the
+ *     start it was actually given: starts[s][r][u] over its free u, starts[s][0][u] over the fixed u.
+ *   RANDOM REPLICA r, R0 <= r < R: exactly replica r of uavhip_search_multistart for the same s and seed
+ *     with assignment_in[s] = starts[s][0]: all of starts[s][0] is converted (and counted in column 3), a
+ *     fixed UAV keeps fixed0[u], every other UAV starts on list index t = (x * M) >> 32, x = word (u & 3)
+ *     of philox4x32_10(counter = {u >> 2, r, s, 0x5354524D}, key = {(uint32_t)seed, (uint32_t)(seed >> 32)}).
+ *     The counter holds r itself: a random replica's J depends on r, s and seed, not on how many given
+ *     starts precede it.
+ *  - R0: 1 <= R0 <= R <= UAVHIP_MULTISTART_MAX_R. starts == NULL is allowed only with R0 == 1 (the empty
+ *    start). With R0 == 1 every output is bitwise uavhip_search_multistart's with assignment_in = starts;
+ *  - assignment_out (required): may alias starts only when R0 == 1 (then [S][N] on both sides, and the
+ *    kernel boundary is the dependence); with R0 > 1 the two must not overlap;
+ *  - column 9 of stats counts the replicas strictly above replica 0's J, given and random alike; r* < R0
+ *    says that a given start won.
+ * Guarantees: those of uavhip_search_assignments_constrained for every replica, with the fixed UAVs where
+ * starts[s][0] puts them; J[s] >= the J of every given start's own constrained search; two calls with the
+ * same arguments give bitwise equal outputs.
+ * UAVHIP_EINVAL: R0 < 1, R0 > R, starts == NULL with R0 > 1, and everything uavhip_search_multistart
+ * refuses. Two launches, asynchronous on `stream`, capturable; the full N <= 64, M <= 128 range; no
+ * allocation, no atomics, no device or grid-wide synchronisation; the env's state and scene and the
+ * inputs are only read. */
+int uavhip_search_multistart_from(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t R, int32_t R0,
+                                  uint64_t seed, int32_t max_exchanges, int32_t max_sweeps, const uint8_t* allowed,
+                                  const uint8_t* fixed, const int32_t* capacity, const int32_t* starts,
+                                  int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats,
+                                  double* J_all, void* workspace, int64_t workspace_bytes, uavhip_stream_t stream);
+
 /* Teacher-forced episodes (k_teacher_steps, teacher.hip): walk every env along a GIVEN allocation,
  * up to n_max steps in ONE launch, and record the window each action was decided on, the action and
  * the env's own reward / done / info -- the training data of uavhip.imitate. The action of a step is

@@ -138,6 +138,9 @@ _SIGS = {
     "uavhip_multistart_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
     "uavhip_search_multistart": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, ctypes.c_uint64, _i32, _i32,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp]),
+    "uavhip_search_multistart_from": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _i32, ctypes.c_uint64,
+                                                     _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     ctypes.c_int64, _vp]),
     "uavhip_teacher_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
     "uavhip_expert_steps": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -30,16 +30,25 @@ a subset DP over the UAVs (uavhip_solve_exact), under the same constraints when 
 restarts = R > 0 (solve and baseline) runs the constrained search R times per scene in one launch
 (uavhip_search_multistart): replica 0 is what the call does without it, the others start from random
 full assignments, and the best J wins -- a near-optimal allocator at every size, constraints included.
+solve(restarts=R, starts="replicas") starts that search from ALL K decoded replicas of a scene instead of
+the chosen one (uavhip_search_multistart_from): replicas 0..K-1 of the search run from the K allocations
+the decode left, the other R - K from random full assignments; refine_stats[:, 8] < K says a policy start
+won, and Allocation.start_J holds every replica's J.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] [--restarts R] prints one JSON line (mean / best J, mean covered, mean steps,
+[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] [--restarts R] [--starts replicas] prints one JSON line (mean / best J, mean covered, mean steps,
 scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
 scenes where the policy beats the baseline; with --exchanges also mean_exchanges and, beside the plain
 mean_J_baseline, mean_J_baseline_exchange; with --optimum, which implies --baseline, also mean_J_optimal, each
 mean J's share of it (baseline_over_optimal, decoded_over_optimal, ...) and the share of scenes where the
 baseline reaches it, baseline_is_optimal; with --restarts R also mean_J_multistart, the baseline with R
 restarts and --exchanges' cap (32 when that is 0), and with --optimum multistart_over_optimal and
-multistart_is_optimal).
+multistart_is_optimal; with --starts replicas, which needs --restarts R >= --samples K >= 2, also
+mean_J_policy_starts -- solve(restarts=R, starts="replicas") at --refine's and --exchanges' caps, 32 where
+they are 0 --, policy_start_wins, the share of scenes where one of the K policy starts is the chosen replica
+(a tie goes to the lowest replica, so to a policy start: read it beside the next key),
+policy_starts_beat_random, the share where its J is strictly above mean_J_multistart's scene at the same R,
+and with --optimum policy_starts_over_optimal and policy_starts_is_optimal).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
@@ -68,6 +77,8 @@ class Allocation:
     steps: torch.Tensor         # [S] int32: decode steps of the chosen replica
     replica_J: torch.Tensor     # [S, K] f64: J of every replica as decoding left it
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
+    start_J: Optional[torch.Tensor] = None  # [S, R] f64: J of every replica of the search (starts="replicas");
+    #                                         placed here so that decoded_J and refine_stats stay the last two fields
     decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
     refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
     #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean;
@@ -77,7 +88,7 @@ class Allocation:
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
                             (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
-                             self.actions, self.decoded_J, self.refine_stats)))
+                             self.actions, self.start_J, self.decoded_J, self.refine_stats)))
 
 
 @dataclass
@@ -211,7 +222,7 @@ class AllocationSolver:
 
     @torch.no_grad()
     def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0,
-              constraints=None, restarts=0):
+              constraints=None, restarts=0, starts="best"):
         """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
         `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
         greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
@@ -235,7 +246,19 @@ class AllocationSolver:
         the constraints when given), replicas 1..R-1 the same search from random full assignments drawn
         with Philox key `seed` -- and the replica with the largest J is kept; refine_stats is [S, 10]: the
         chosen replica's eight counters, its index, the replicas above replica 0. restarts = 0 launches
-        nothing new and changes no result."""
+        nothing new and changes no result.
+        starts = "replicas" (needs refine > 0, samples K >= 2 and restarts R >= K; "best", the default, is
+        everything above, bitwise): the search starts from ALL K decoded replicas of a scene, not only
+        the chosen one (uavhip_search_multistart_from with R0 = K). Replica k < K of the search runs from
+        what replica k of the decode assigned -- env.assigned_target_ids() as [S, K, N], an unfinished
+        replica included with what it assigned so far --, replicas K..R-1 from random full assignments
+        drawn with Philox key `seed`; with constraints the committed UAVs' fixed ids are laid over every
+        one of the K starts. decoded_J, best_replica and replica_J stay select_best's; refine_stats[:, 8]
+        is the chosen replica r* of the search (r* < K: a policy start won) and start_J [S, R] every
+        replica's J. The start of the call with restarts = 0 is one of the K (replica best_replica), its
+        search is that replica's bit for bit, so per scene J >= that call's J wherever a replica finished."""
+        if starts not in ("best", "replicas"):
+            raise ValueError(f"solve: starts must be 'best' or 'replicas' (got {starts!r})")
         refine, exchanges, restarts = int(refine), int(exchanges), int(restarts)
         if not 0 <= restarts <= _lib.MULTISTART_MAX_R:
             raise ValueError(f"solve: restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
@@ -250,6 +273,12 @@ class AllocationSolver:
         _check_constraints("solve", constraints)
         if constraints is not None and refine == 0:
             raise ValueError("solve: constraints need refine > 0 (the decode ignores them; the search applies them)")
+        if starts == "replicas":
+            if self.K < 2:
+                raise ValueError(f"solve: starts='replicas' needs samples >= 2 (got {self.K}: one replica is starts='best')")
+            if restarts < self.K:
+                raise ValueError(f"solve: starts='replicas' needs restarts={restarts} >= samples={self.K} "
+                                 f"(one replica of the search per decoded replica)")  # so restarts > 0: refine > 0
         scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
         allowed = capacity = fixed_ids = None
@@ -271,6 +300,18 @@ class AllocationSolver:
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
             if refine == 0:
                 return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+            if starts == "replicas":
+                given = env.assigned_target_ids().to(torch.int32).view(S, K, self.N)  # scene-major already: no gather
+                fixed = None
+                if fixed_ids is not None:
+                    given, fixed = _with_fixed(given, fixed_ids.view(S, 1, self.N), None, env.device)
+                    fixed = fixed.view(S, self.N)
+                start_J = torch.empty(S, restarts, dtype=torch.float64, device=env.device)
+                refined, rJ, rcov, stats = env.search_assignments_multistart(
+                    None, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
+                    max_exchanges=exchanges, max_sweeps=refine, J_all=start_J, starts=given.contiguous())
+                return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats,
+                                  start_J=start_J)
             if restarts > 0:
                 start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
                 refined, rJ, rcov, stats = env.search_assignments_multistart(
@@ -385,11 +426,18 @@ def main(argv=None):
     ap.add_argument("--restarts", type=int, default=0, metavar="R",
                     help="also the baseline as the best of R restarts of the exchange search (uavhip_search_multistart; "
                          "--exchanges' cap, or 32 when that is 0): mean_J_multistart; implies --baseline")
+    ap.add_argument("--starts", choices=("best", "replicas"), default="best",
+                    help="replicas (needs --restarts R >= --samples K >= 2): also the search started from all K decoded "
+                         "replicas of each scene plus R - K random starts (uavhip_search_multistart_from; --refine's and "
+                         "--exchanges' caps, 32 where they are 0): mean_J_policy_starts, policy_start_wins, "
+                         "policy_starts_beat_random")
     a = ap.parse_args(argv)
     if a.exchanges < 0:
         ap.error("--exchanges must be >= 0")
     if not 0 <= a.restarts <= _lib.MULTISTART_MAX_R:
         ap.error(f"--restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
+    if a.starts == "replicas" and not 2 <= a.samples <= a.restarts:
+        ap.error("--starts replicas needs --restarts R >= --samples K >= 2")
     if a.optimum and a.uavs > _lib.EXACT_MAX_N:
         ap.error(f"--optimum needs --uavs <= {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
     if not torch.cuda.is_available():
@@ -423,6 +471,12 @@ def main(argv=None):
         if a.restarts > 0:
             bm = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges or 32, restarts=a.restarts).cpu()
             out.update(mean_J_multistart=float(bm.J.mean()))
+        if a.starts == "replicas":
+            ps = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine or 32, exchanges=a.exchanges or 32,
+                              restarts=a.restarts, starts="replicas").cpu()
+            out.update(mean_J_policy_starts=float(ps.J.mean()),
+                       policy_start_wins=float((ps.refine_stats[:, 8] < a.samples).double().mean()),
+                       policy_starts_beat_random=float((ps.J > bm.J).double().mean()))
     if a.optimum:
         o = solver.optimum(num_scenes=a.scenes, seed=a.seed).cpu()
         best = float(o.J.mean())
@@ -439,6 +493,8 @@ def main(argv=None):
             out.update(baseline_exchange_over_optimal=float(bx.J.mean()) / best, baseline_exchange_is_optimal=reaches(bx))
         if a.restarts > 0:
             out.update(multistart_over_optimal=float(bm.J.mean()) / best, multistart_is_optimal=reaches(bm))
+        if a.starts == "replicas":
+            out.update(policy_starts_over_optimal=float(ps.J.mean()) / best, policy_starts_is_optimal=reaches(ps))
     print(json.dumps(out))
 
 

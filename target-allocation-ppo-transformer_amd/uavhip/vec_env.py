@@ -348,13 +348,18 @@ class VecUAVEnv:
 
     def search_assignments_multistart(self, assignment=None, allowed=None, fixed=None, capacity=None, restarts=16,
                                       seed=0, stride=1, rows=None, max_exchanges=32, max_sweeps=32, out=None, J=None,
-                                      covered=None, stats=None, J_all=None):
+                                      covered=None, stats=None, J_all=None, starts=None):
         """uavhip_search_multistart: per row the best of `restarts` = R independent runs (replicas) of
         search_assignments_constrained -- replica 0 from `assignment` (its result bit for bit), the
         others from uniform random full assignments drawn with Philox key `seed` (a fixed UAV keeps
         the target `assignment` gives it in every replica); the caps hold per replica and the replica
         with the largest J wins, the lowest index among equal J (include/uavhip.h has the rule). Rows,
         stride and the three constraint arrays are search_assignments_constrained's, None included.
+        starts [rows, R0, N] int32 target ids or -1, instead of `assignment` (uavhip_search_multistart_from):
+        replicas 0 .. R0 - 1 run from the row's R0 given starts, each the constrained search from its
+        own start, and replicas R0 .. R - 1 are the random ones, replica r what it is without `starts`;
+        a fixed UAV keeps the target starts[:, 0] gives it in every replica. Needs restarts >= R0.
+        Without `starts` the call is what it was, launch for launch.
         Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32, stats
         [rows, 10] int32: the chosen replica's eight counters of the constrained search, its index,
         the number of replicas strictly above replica 0's J). J_all [rows, R] f64, when given, receives
@@ -369,6 +374,21 @@ class VecUAVEnv:
         seed = int(seed)
         if not 0 <= seed < 2 ** 64:
             raise ValueError(f"{fn}: seed={seed} must be in [0, 2^64)")
+        R0 = 0
+        if starts is not None:
+            if assignment is not None:
+                raise ValueError(f"{fn}: pass assignment or starts, not both")
+            ok = isinstance(starts, torch.Tensor) and starts.dim() == 3 and starts.shape[1] >= 1 and \
+                tuple(starts.shape[::2]) == (S, self.N)
+            if ok:
+                check_out(starts, "starts", torch.int32, starts.shape, self.device)
+            else:
+                got = f"{starts.dtype} {tuple(starts.shape)}" if isinstance(starts, torch.Tensor) else type(starts).__name__
+                raise ValueError(f"starts: need a contiguous torch.int32 tensor [{S}, R0 >= 1, {self.N}] on {self.device} "
+                                 f"(got {got})")
+            R0 = int(starts.shape[1])
+            if R < R0:
+                raise ValueError(f"{fn}: restarts={R} must be >= the {R0} given starts")
         check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
         check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
         check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
@@ -380,6 +400,12 @@ class VecUAVEnv:
         ws = self.__dict__.get("_multistart_ws")
         if ws is None or ws.numel() < nbytes:
             ws = self._multistart_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if starts is not None:
+            check(LIB.uavhip_search_multistart_from(self.desc, stride, S, R, R0, seed, max_exchanges, max_sweeps,
+                                                    ptr(allowed), ptr(fixed), ptr(capacity), ptr(starts), ptr(out),
+                                                    ptr(J), ptr(covered), ptr(stats), ptr(J_all), ptr(ws), ws.numel(),
+                                                    stream_handle()), "uavhip_search_multistart_from")
+            return out, J, covered, stats
         check(LIB.uavhip_search_multistart(self.desc, stride, S, R, seed, max_exchanges, max_sweeps, ptr(allowed),
                                            ptr(fixed), ptr(capacity), ptr(assignment), ptr(out), ptr(J), ptr(covered),
                                            ptr(stats), ptr(J_all), ptr(ws), ws.numel(), stream_handle()),
