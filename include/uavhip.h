@@ -628,6 +628,85 @@ int uavhip_solve_exact(const uavhip_env* env, int32_t env_stride, int32_t S, con
                        int32_t* assignment_out, double* J, int32_t* covered, int32_t* stats, void* workspace,
                        int64_t workspace_bytes, uavhip_stream_t stream);
 
+/* The optimum of J(X) over a NEIGHBOURHOOD (k_exact_free_*, exact_free.hip): the subset DP of
+ * uavhip_solve_exact over a row's free UAVs only, everyone else held where assignment_in puts them, for
+ * the full N <= 64, M <= 128. The DP's cost depends on the UAVs that may move (3^bits steps a target), and
+ * a held UAV changes only the value of its target, so "these K <= 16 UAVs may go anywhere, the others
+ * stay" is solved exactly at any N: a neighbourhood of (M + 1)^K assignments that contains every single
+ * move, exchange, 3-cycle and ejection chain among the K. The rule is uavhip_solve_exact's word for word
+ * -- the same feasible set, the same allowed [S][N][M] / fixed [S][N] / capacity [S][M] arrays (each
+ * nullable), the same id conversion -- with these differences:
+ *   FREE LIST of a row: the UAVs u with fixed[s][u] == 0 (all of them when fixed == NULL), ascending. The
+ *     first K = min(max_free, N) of them are in the DP, and bit b of a set is the b-th of them. Any
+ *     further free UAV is HELD exactly as a fixed one is: it keeps the target its input converts to,
+ *     whatever the constraints say (fixed is device data: the host cannot refuse on it; stats column 3
+ *     counts them).
+ *   HELD UAVs (fixed, or free beyond the first K): with H_t the held UAVs on target t,
+ *       q_fix[t] = prod_{u in H_t} (1.0 - P[u][t])      in ascending u, starting from 1.0
+ *     and a stage is uavhip_solve_exact's with v[t] * q_fix[t] where that one uses v[t]:
+ *       val_t(H_t + T) - val_t(H_t) = (v[t] q_fix[t]) (1 - prod_{u in T} (1 - P[u][t])) - w sum_{u in T} c[u]
+ *     The free UAVs on t obey allowed and number at most max(capacity[t], |H_t|) - |H_t| (capacity < 0
+ *     as 0; no limit without a capacity array).
+ *   TIE-BREAK: of equal maxima the smallest T as an integer over the free-list bits; the result is read
+ *     back from t = M-1 down, as there.
+ *   A row with fewer than K free UAVs runs the same tables with dead high bits that no target may hold;
+ *     the live bits are the lowest, the arithmetic of a set does not involve the dead ones, and no output
+ *     depends on K beyond which UAVs are in the DP.
+ * With N <= 16, fixed == NULL and max_free >= N every v[t] * 1.0 is v[t] and assignment_out, J, covered and
+ * stats columns 0-1 are bitwise uavhip_solve_exact's. The result is never below the input's J beyond the
+ * rounding of the DP's own sums when the input is feasible (the input is one of the assignments searched).
+ *  - max_free: 1 <= max_free <= UAVHIP_EXACT_FREE_MAX;
+ *  - env, env_stride, S, assignment_out, J, covered (all required): as uavhip_solve_exact; J, covered and
+ *    the ids come from the code uavhip_refine_assignments ends with, so J is bitwise
+ *    uavhip_refine_assignments(assignment_out, max_sweeps = 0)'s;
+ *  - assignment_in [S][N] int32 (nullable: the empty start, every held UAV on none): where the held
+ *    UAVs stand; a free UAV's input is not looked at. Required when fixed != NULL;
+ *  - stats [S][4] int32 (nullable): invalid input ids; fixed_conflicts, counted over the held UAVs as
+ *    pass 1 of uavhip_search_assignments_constrained counts them over the fixed ones; free UAVs in the
+ *    DP; free UAVs held by overflow;
+ *  - workspace: device memory, 16-byte aligned, contents unspecified before and after. One row needs
+ *    uavhip_exact_free_workspace_bytes(K, M, 1) bytes -- uavhip_solve_exact's layout with K in place of N:
+ *    two tables of 2^K doubles, the choice table [M][2^K] of uint16, then M 16-byte target records (the
+ *    sets, the capacity left, v q_fix) and the 16-byte free list (1088 KiB + 2064 B at K = 12, M = 128).
+ *    A workspace that holds fewer than S rows is no error: the rows run in chunks. That function returns
+ *    -1 unless 1 <= max_free <= 16, 1 <= M <= 128 and rows >= 1.
+ * Nothing depends on timing: no atomics, one lane writes each value, two calls give bitwise equal outputs.
+ * UAVHIP_EINVAL: the row bounds, max_free out of range, a required output NULL, fixed without
+ * assignment_in, a workspace that is NULL, misaligned or smaller than one row's need. Per chunk one
+ * prepare launch, M stage launches, one read-back launch. Asynchronous on `stream`, capturable; no
+ * allocation, no device or grid-wide synchronisation; the env and the inputs are only read. */
+#define UAVHIP_EXACT_FREE_MAX 16
+int64_t uavhip_exact_free_workspace_bytes(int32_t max_free, int32_t M, int32_t rows);
+int uavhip_solve_exact_free(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t max_free,
+                            const uint8_t* allowed, const uint8_t* fixed, const int32_t* capacity,
+                            const int32_t* assignment_in, int32_t* assignment_out, double* J, int32_t* covered,
+                            int32_t* stats, void* workspace, int64_t workspace_bytes, uavhip_stream_t stream);
+
+/* The free set of one round of a large-neighbourhood search (k_neighbourhood_pick, exact_free.hip),
+ * chosen on device so that a loop of pick + uavhip_solve_exact_free needs no host synchronisation.
+ * Writes fixed_out [S][N] uint8: 1 = held, 0 = free -- uavhip_solve_exact_free's `fixed`.
+ *   KEYS of row s:  ku[u] = word (u & 3) of philox4x32_10(counter = {u >> 2, round, s, 0x4E424855},
+ *                           key = {(uint32_t)seed, (uint32_t)(seed >> 32)}),
+ *                   kt[t] = the same with 0x4E424854 over the target's LIST index t
+ *     (the Philox of uavhip_search_multistart).
+ *   The UAVs with fixed_in[s][u] != 0 are always held and never counted in K. The others are sorted by
+ *   the mode's key, ascending, and the first min(K, their number) become free:
+ *     UAVHIP_NBH_RANDOM:   (ku[u], u);
+ *     UAVHIP_NBH_TARGETS:  (g[u], ku[u], u), with g[u] = 0 for a UAV whose assignment converts to none
+ *       (-1, or an id of no target) and otherwise 1 + the rank of kt[a[u]] among the M target keys, ties
+ *       by lower index: the idle UAVs first, then the whole crews of randomly chosen targets.
+ *  - assignment [S][N] int32 (nullable: every UAV idle): target ids or -1, read in TARGETS mode only and
+ *    converted as uavhip_refine_assignments converts them; fixed_in [S][N] uint8 (nullable);
+ *    fixed_out (required) may alias fixed_in.
+ * Deterministic; the env and the inputs are only read. UAVHIP_EINVAL: the row bounds, K outside
+ * 1..UAVHIP_EXACT_FREE_MAX, a mode that is neither, fixed_out NULL. One launch, one wave per row,
+ * asynchronous on `stream`, capturable. */
+#define UAVHIP_NBH_RANDOM 0
+#define UAVHIP_NBH_TARGETS 1
+int uavhip_neighbourhood_pick(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t K, int32_t mode,
+                              uint32_t round, uint64_t seed, const int32_t* assignment, const uint8_t* fixed_in,
+                              uint8_t* fixed_out, uavhip_stream_t stream);
+
 /* Multi-start search (k_search_multistart / k_multistart_select, search_multistart.hip): per row the
  * best of R independent runs ("replicas") of uavhip_search_assignments_constrained's rule, replica 0
  * from assignment_in and the others from random full assignments. A local search stops at the first

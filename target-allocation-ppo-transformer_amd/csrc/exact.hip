@@ -10,7 +10,7 @@
 //   k_exact_stage      one launch per target t: D_t -> D_{t+1} and choice_t, one wave per tile;
 //   k_exact_backtrack  one wave per row: t = M-1..0, T = choice_t[S], S <- S \ T, then finish.
 //
-// A stage's tile: the UAV bits split into L = min(N, 10) low and H = N - L high bits, and one wave
+// A stage's tile (exact_stage_tile, exact_device.hpp: shared with exact_free.hip): the UAV bits split into L = min(N, 10) low and H = N - L high bits, and one wave
 // (one 64-thread workgroup) owns the 2^L states of one high part Sh. It loops over the feasible
 // Th <= Sh (descending), and per Th keeps in LDS
 //   tile[Sl]  = D_t[Sh \ Th][Sl]                                   (staged, 8 KB)
@@ -25,18 +25,10 @@
 // state), and the lists are built at compile time by longest-processing-time-first over the states in
 // descending popcount, so the lanes' step totals are equal to within the largest state: at L = 10 the
 // fullest lane runs 1024 steps against a mean of 3^10 / 64 = 923 (90 % lane use); DESIGN.md 9i.
-#include "refine_device.hpp"
+#include "exact_device.hpp"
 
 namespace uavhip {
 namespace {
-
-constexpr int kExactLowBits = 10;
-constexpr int kExactTile = 1 << kExactLowBits;
-
-struct ExactMask {
-    uint16_t may, must;  // bit u: UAV u may be on the target (free and allowed, or fixed to it) / is fixed to it
-    int32_t cap;         // max(capacity, fixed UAVs on it); N without a capacity array
-};
 
 struct ExactLayout {
     long long d_bytes, choice_off, mask_off, row_bytes;
@@ -48,67 +40,6 @@ inline ExactLayout exact_layout(int N, int M) {
     w.mask_off = (w.choice_off + ((long long)M * (long long)sizeof(uint16_t) << N) + 7) & ~7ll;
     w.row_bytes = (w.mask_off + (long long)M * (long long)sizeof(ExactMask) + 15) & ~15ll;
     return w;
-}
-
-// ------------------------------------------------------------------ the lanes' state lists
-// States of L bits in descending popcount, each given to the lane with the fewest steps so far (the
-// lowest such lane); lane l walks list[off[l]] .. list[off[l + 1] - 1].
-template <int L>
-struct ExactSched {
-    uint16_t off[kWave + 1];
-    uint16_t list[1 << L];
-};
-template <int L>
-constexpr ExactSched<L> make_exact_sched() {
-    ExactSched<L> s{};
-    int load[kWave] = {}, count[kWave] = {};
-    uint16_t lane_of[1 << L] = {};
-    for (int k = L; k >= 0; --k)
-        for (int st = 0; st < (1 << L); ++st) {
-            int pc = 0;
-            for (int b = 0; b < L; ++b) pc += st >> b & 1;
-            if (pc != k) continue;
-            int best = 0;
-            for (int l = 1; l < kWave; ++l)
-                if (load[l] < load[best]) best = l;
-            load[best] += 1 << k;
-            ++count[best];
-            lane_of[st] = (uint16_t)best;
-        }
-    int at = 0;
-    for (int l = 0; l < kWave; ++l) {
-        s.off[l] = (uint16_t)at;
-        at += count[l];
-    }
-    s.off[kWave] = (uint16_t)at;
-    int fill[kWave] = {};
-    for (int k = L; k >= 0; --k)  // a lane's own list in descending popcount too
-        for (int st = 0; st < (1 << L); ++st) {
-            int pc = 0;
-            for (int b = 0; b < L; ++b) pc += st >> b & 1;
-            if (pc != k) continue;
-            const int l = lane_of[st];
-            s.list[s.off[l] + fill[l]++] = (uint16_t)st;
-        }
-    return s;
-}
-#define UAVHIP_EXACT_SCHED(L) __device__ const ExactSched<L> g_exact_sched_##L = make_exact_sched<L>();
-UAVHIP_EXACT_SCHED(1) UAVHIP_EXACT_SCHED(2) UAVHIP_EXACT_SCHED(3) UAVHIP_EXACT_SCHED(4) UAVHIP_EXACT_SCHED(5)
-UAVHIP_EXACT_SCHED(6) UAVHIP_EXACT_SCHED(7) UAVHIP_EXACT_SCHED(8) UAVHIP_EXACT_SCHED(9) UAVHIP_EXACT_SCHED(10)
-
-__device__ __forceinline__ void exact_sched(int L, const uint16_t*& off, const uint16_t*& list) {
-#define UAVHIP_EXACT_PICK(K)         \
-    case K:                          \
-        off = g_exact_sched_##K.off; \
-        list = g_exact_sched_##K.list; \
-        break;
-    switch (L) {
-        UAVHIP_EXACT_PICK(1) UAVHIP_EXACT_PICK(2) UAVHIP_EXACT_PICK(3) UAVHIP_EXACT_PICK(4) UAVHIP_EXACT_PICK(5)
-        UAVHIP_EXACT_PICK(6) UAVHIP_EXACT_PICK(7) UAVHIP_EXACT_PICK(8) UAVHIP_EXACT_PICK(9)
-        default:
-            off = g_exact_sched_10.off;
-            list = g_exact_sched_10.list;
-    }
 }
 
 // ------------------------------------------------------------------ prepare
@@ -179,10 +110,8 @@ __global__ __launch_bounds__(64 * kRefineWaves) void k_exact_prepare(
 __global__ __launch_bounds__(kWave) void k_exact_stage(uavhip_env env, int stride, int s0, int t, int first,
                                                        char* __restrict__ ws, long long row_bytes, long long d_bytes,
                                                        long long choice_off, long long mask_off) {
-    __shared__ double tile[kExactTile], comb[kExactTile], accv[kExactTile];
-    __shared__ uint16_t accc[kExactTile];
     const int N = env.N, M = env.M, lane = threadIdx.x;
-    const int L = N < kExactLowBits ? N : kExactLowBits, H = N - L, nl = 1 << L;
+    const int L = N < kExactLowBits ? N : kExactLowBits, H = N - L;
     const int r = blockIdx.x >> H;
     const unsigned Sh = blockIdx.x & ((1u << H) - 1);
     char* rw = ws + (long long)r * row_bytes;
@@ -190,7 +119,6 @@ __global__ __launch_bounds__(kWave) void k_exact_stage(uavhip_env env, int strid
     double* dnext = reinterpret_cast<double*>(rw + (long long)((t + 1) & 1) * d_bytes);
     uint16_t* choice = reinterpret_cast<uint16_t*>(rw + choice_off) + ((long long)t << N);
     const ExactMask mk = reinterpret_cast<const ExactMask*>(rw + mask_off)[t];
-    const double ninf = -__builtin_huge_val();
 
     // lane u: 1 - P[u][t] and omega c[u] of the row's active scene
     const long long e = (long long)(s0 + r) * stride;
@@ -203,106 +131,7 @@ __global__ __launch_bounds__(kWave) void k_exact_stage(uavhip_env env, int strid
         wc = env.prm[UAVHIP_PRM_OMEGA] * env.uav_cost[sb * N + lane];
     }
 
-    const unsigned lo = nl - 1;
-    const unsigned mayl = mk.may & lo, mustl = mk.must & lo, mayh = mk.may >> L, musth = mk.must >> L;
-    for (int i = lane; i < nl; i += kWave) {
-        accv[i] = ninf;
-        accc[i] = 0;
-    }
-    // the lane's share of ql / cl: the low six bits of a tile index lane + 64 k are the lane's
-    double qlane = 1.0, clane = 0.0;
-    for (int b = 0; b < (L < 6 ? L : 6); ++b) {
-        const double ob = readlane_d(om, b), cb = readlane_d(wc, b);
-        if (lane >> b & 1) {
-            qlane = qlane * ob;
-            clane = clane + cb;
-        }
-    }
-    const uint16_t *off, *list;
-    exact_sched(L, off, list);
-    const int k0 = off[lane], k1 = off[lane + 1];
-
-    if ((Sh & musth) == musth) {  // else no feasible T for any state of the tile: every D stays -inf
-        const unsigned Eh = Sh & mayh & ~musth;
-        unsigned Xh = Eh;
-        for (;;) {
-            const unsigned Th = musth | Xh;
-            const int nh = __popc(Th);
-            if (nh <= mk.cap) {
-                double qh = 1.0, chs = 0.0;
-                for (int b = 0; b < H; ++b)
-                    if (Th >> b & 1) {
-                        qh = qh * readlane_d(om, L + b);
-                        chs = chs + readlane_d(wc, L + b);
-                    }
-                const double A = v - chs, B = v * qh;
-                const double* src = dprev + ((long long)(Sh ^ Th) << L);
-                __syncthreads();  // the previous Th's readers are done with tile / comb
-                for (int k = 0; (k << 6) < nl; ++k) {
-                    const int i = lane + (k << 6);
-                    if (i >= nl) break;
-                    tile[i] = first ? 0.0 : src[i];
-                    double qk = 1.0, ck = 0.0;
-                    for (int b = 6; b < L; ++b)
-                        if (k >> (b - 6) & 1) {
-                            qk = qk * readlane_d(om, b);
-                            ck = ck + readlane_d(wc, b);
-                        }
-                    const double val = (A - (clane + ck)) - B * (qlane * qk);
-                    comb[i] = nh + __popc(i) <= mk.cap ? val : ninf;
-                }
-                __syncthreads();
-
-                // the flattened walk over the lane's states
-                int k = k0;
-                bool active = false;
-                unsigned S = 0, E = 0, X = 0;
-                double best = ninf;
-                unsigned bestT = 0;
-                auto take = [&]() {  // the next state of the list whose low part holds the fixed UAVs
-                    active = false;
-                    while (k < k1) {
-                        S = list[k];
-                        if ((S & mustl) == mustl) {
-                            active = true;
-                            E = S & mayl & ~mustl;
-                            X = E;
-                            best = accv[S];
-                            bestT = accc[S];
-                            break;
-                        }
-                        ++k;
-                    }
-                };
-                take();
-                while (active) {
-                    const unsigned T = mustl | X;
-                    const double cand = tile[S ^ T] + comb[T];
-                    if (cand >= best) {  // descending T: of equal values the smallest T stays
-                        best = cand;
-                        bestT = Th << L | T;
-                    }
-                    if (X == 0) {
-                        accv[S] = best;
-                        accc[S] = (uint16_t)bestT;
-                        ++k;
-                        take();
-                    } else {
-                        X = (X - 1) & E;
-                    }
-                }
-            }
-            if (Xh == 0) break;
-            Xh = (Xh - 1) & Eh;
-        }
-    }
-    __syncthreads();
-    double* dst = dnext + ((long long)Sh << L);
-    uint16_t* cdst = choice + ((long long)Sh << L);
-    for (int i = lane; i < nl; i += kWave) {
-        dst[i] = accv[i];
-        cdst[i] = accc[i];
-    }
+    exact_stage_tile(N, Sh, first, v, om, wc, mk, dprev, dnext, choice);
 }
 
 // ------------------------------------------------------------------ backtrack

@@ -23,6 +23,8 @@ STATE_DIM = 14
 OBS_FLOATS = SEQ_LEN * STATE_DIM
 MAX_N, MAX_M, MAX_OBSTACLES = 64, 128, 8
 EXACT_MAX_N = 16  # UAVHIP_EXACT_MAX_N: the most UAVs uavhip_solve_exact takes
+EXACT_FREE_MAX = 16  # UAVHIP_EXACT_FREE_MAX: the most free UAVs uavhip_solve_exact_free's DP takes
+NBH = dict(random=0, targets=1)  # UAVHIP_NBH_RANDOM / UAVHIP_NBH_TARGETS: uavhip_neighbourhood_pick's modes
 MULTISTART_MAX_R = 1024  # UAVHIP_MULTISTART_MAX_R: the most replicas a row of uavhip_search_multistart runs
 ENV_ONE_PER_WAVE, ENV_OBS_F16, ENV_NO_REPLAY = 1, 2, 4  # uavhip_env.flags bits
 STEP_HOLD = 2  # UAVHIP_STEP_HOLD: the decode kernel's env-step mode (a finished env is held)
@@ -135,6 +137,11 @@ _SIGS = {
     "uavhip_exact_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
     "uavhip_solve_exact": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, ctypes.c_int64, _vp]),
+    "uavhip_exact_free_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
+    "uavhip_solve_exact_free": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, ctypes.c_int64, _vp]),
+    "uavhip_neighbourhood_pick": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, _i32, ctypes.c_uint32,
+                                                 ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "uavhip_multistart_workspace_bytes": (ctypes.c_int64, [_i32, _i32, _i32]),
     "uavhip_search_multistart": (ctypes.c_int, [ctypes.POINTER(EnvDesc), _i32, _i32, _i32, ctypes.c_uint64, _i32, _i32,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp]),

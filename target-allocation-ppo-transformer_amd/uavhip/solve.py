@@ -34,9 +34,15 @@ solve(restarts=R, starts="replicas") starts that search from ALL K decoded repli
 the chosen one (uavhip_search_multistart_from): replicas 0..K-1 of the search run from the K allocations
 the decode left, the other R - K from random full assignments; refine_stats[:, 8] < K says a policy start
 won, and Allocation.start_J holds every replica's J.
+lns_rounds = L > 0 (solve and baseline) runs a large-neighbourhood search after whatever search the call
+already does, under the same constraints (VecUAVEnv.lns_assignments): L times, lns_free = K <= 16 UAVs of
+the scene are freed and re-placed at the optimum of J over all their (M + 1)^K placements
+(uavhip_solve_exact_free, at every N <= 64), the others held, and a scene keeps the new allocation only
+where its J is strictly larger. Allocation.lns_J_before holds the J going in.
 
 Command line: python -m uavhip.solve --checkpoint PATH --scenes S --samples K [--seed SEED]
-[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] [--restarts R] [--starts replicas] prints one JSON line (mean / best J, mean covered, mean steps,
+[--refine SWEEPS] [--exchanges X] [--baseline] [--optimum] [--restarts R] [--starts replicas]
+[--lns ROUNDS --lns-free K --lns-mode {random,targets}] prints one JSON line (mean / best J, mean covered, mean steps,
 scenes/s; with the flags also mean_J_decoded / mean_J_refined / mean_J_baseline and the share of
 scenes where the policy beats the baseline; with --exchanges also mean_exchanges and, beside the plain
 mean_J_baseline, mean_J_baseline_exchange; with --optimum, which implies --baseline, also mean_J_optimal, each
@@ -48,12 +54,15 @@ mean_J_policy_starts -- solve(restarts=R, starts="replicas") at --refine's and -
 they are 0 --, policy_start_wins, the share of scenes where one of the K policy starts is the chosen replica
 (a tie goes to the lowest replica, so to a policy start: read it beside the next key),
 policy_starts_beat_random, the share where its J is strictly above mean_J_multistart's scene at the same R,
-and with --optimum policy_starts_over_optimal and policy_starts_is_optimal).
+and with --optimum policy_starts_over_optimal and policy_starts_is_optimal; with --lns ROUNDS, which implies
+--baseline, also mean_J_lns -- the baseline with --exchanges' cap, 32 when that is 0, then ROUNDS rounds of
+the large-neighbourhood search with --lns-free UAVs free --, lns_improved, the share of scenes it strictly
+improved, and with --optimum lns_over_optimal and lns_is_optimal).
 
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
@@ -79,6 +88,7 @@ class Allocation:
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
     start_J: Optional[torch.Tensor] = None  # [S, R] f64: J of every replica of the search (starts="replicas");
     #                                         placed here so that decoded_J and refine_stats stay the last two fields
+    lns_J_before: Optional[torch.Tensor] = None  # [S] f64: J going into the large-neighbourhood search (lns_rounds > 0)
     decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
     refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
     #                                              [S, 6] with exchanges > 0: + exchanges made, scan clean;
@@ -88,7 +98,7 @@ class Allocation:
     def cpu(self):
         return Allocation(*(None if t is None else t.cpu() for t in
                             (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
-                             self.actions, self.start_J, self.decoded_J, self.refine_stats)))
+                             self.actions, self.start_J, self.lns_J_before, self.decoded_J, self.refine_stats)))
 
 
 @dataclass
@@ -121,6 +131,16 @@ class Constraints:
 def _check_constraints(what, constraints):
     if constraints is not None and not isinstance(constraints, Constraints):
         raise ValueError(f"{what}: constraints must be a uavhip.solve.Constraints (got {type(constraints).__name__})")
+
+
+def _check_lns(what, rounds, free, mode):
+    """The lns_* arguments of solve / baseline, before any device call."""
+    if rounds < 0:
+        raise ValueError(f"{what}: lns_rounds must be >= 0")
+    if rounds > 0 and not 1 <= free <= _lib.EXACT_FREE_MAX:
+        raise ValueError(f"{what}: lns_free={free} must be in [1, {_lib.EXACT_FREE_MAX}]")
+    if rounds > 0 and mode not in _lib.NBH:
+        raise ValueError(f"{what}: lns_mode must be one of {sorted(_lib.NBH)} (got {mode!r})")
 
 
 def _with_fixed(assignment, fixed_ids, shape, device):
@@ -220,9 +240,20 @@ class AllocationSolver:
             self._generate_scenes(env, S, seed)
         return env
 
+    def _lns(self, env, alloc, S, seed, rounds, free, mode, allowed, capacity, fixed_ids):
+        """`alloc` after `rounds` rounds of the large-neighbourhood search from its assignment, the
+        committed UAVs held; alloc itself when rounds == 0."""
+        if rounds == 0:
+            return alloc
+        fixed = None if fixed_ids is None else (fixed_ids != -2).to(torch.uint8)
+        assignment, J, covered, _ = env.lns_assignments(alloc.assignment, rounds=rounds, free=free, mode=mode,
+                                                        seed=seed & (2 ** 64 - 1), allowed=allowed, fixed=fixed,
+                                                        capacity=capacity, stride=self.K, rows=S)
+        return replace(alloc, assignment=assignment, J=J, covered=covered, lns_J_before=alloc.J)
+
     @torch.no_grad()
     def solve(self, scenes=None, num_scenes=None, seed=None, max_steps=None, trace=False, refine=0, exchanges=0,
-              constraints=None, restarts=0, starts="best"):
+              constraints=None, restarts=0, starts="best", lns_rounds=0, lns_free=12, lns_mode="targets"):
         """Decode `scenes` (host scene dicts in the tests/golden / scene.generate_scene layout) or
         `num_scenes` on-device scenes drawn with `seed`; K = samples replicas each (replica 0
         greedy, the rest sampled with Philox key `seed`), at most max_steps steps (default N * M,
@@ -256,7 +287,14 @@ class AllocationSolver:
         one of the K starts. decoded_J, best_replica and replica_J stay select_best's; refine_stats[:, 8]
         is the chosen replica r* of the search (r* < K: a policy start won) and start_J [S, R] every
         replica's J. The start of the call with restarts = 0 is one of the K (replica best_replica), its
-        search is that replica's bit for bit, so per scene J >= that call's J wherever a replica finished."""
+        search is that replica's bit for bit, so per scene J >= that call's J wherever a replica finished.
+        lns_rounds = L > 0: after all of the above, L rounds of VecUAVEnv.lns_assignments from the call's
+        assignment -- lns_free UAVs (1..16) freed per round by rule lns_mode ("targets" or "random", Philox
+        key `seed`) and re-placed at the optimum of their neighbourhood, under the constraints when given,
+        the committed UAVs held. assignment / J / covered are then the search's, lns_J_before the J going
+        in; J >= lns_J_before in every scene. lns_rounds = 0 launches nothing more and changes nothing."""
+        lns_rounds, lns_free = int(lns_rounds), int(lns_free)
+        _check_lns("solve", lns_rounds, lns_free, lns_mode)
         if starts not in ("best", "replicas"):
             raise ValueError(f"solve: starts must be 'best' or 'replicas' (got {starts!r})")
         refine, exchanges, restarts = int(refine), int(exchanges), int(restarts)
@@ -273,6 +311,8 @@ class AllocationSolver:
         _check_constraints("solve", constraints)
         if constraints is not None and refine == 0:
             raise ValueError("solve: constraints need refine > 0 (the decode ignores them; the search applies them)")
+        lns = lambda alloc: self._lns(env, alloc, S, seed, lns_rounds, lns_free, lns_mode, allowed, capacity,  # noqa: E731
+                                      fixed_ids)
         if starts == "replicas":
             if self.K < 2:
                 raise ValueError(f"solve: starts='replicas' needs samples >= 2 (got {self.K}: one replica is starts='best')")
@@ -299,7 +339,7 @@ class AllocationSolver:
             replica_J = env.dstate[:, _lib.DST["J"]].reshape(S, K).clone()
             steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
             if refine == 0:
-                return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+                return lns(Allocation(assignment, J, covered, best, steps, replica_J, actions))
             if starts == "replicas":
                 given = env.assigned_target_ids().to(torch.int32).view(S, K, self.N)  # scene-major already: no gather
                 fixed = None
@@ -310,8 +350,8 @@ class AllocationSolver:
                 refined, rJ, rcov, stats = env.search_assignments_multistart(
                     None, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
                     max_exchanges=exchanges, max_sweeps=refine, J_all=start_J, starts=given.contiguous())
-                return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats,
-                                  start_J=start_J)
+                return lns(Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J,
+                                      refine_stats=stats, start_J=start_J))
             if restarts > 0:
                 start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
                 refined, rJ, rcov, stats = env.search_assignments_multistart(
@@ -326,11 +366,11 @@ class AllocationSolver:
                                                                   max_sweeps=refine)
             else:
                 refined, rJ, rcov, stats = env.refine_assignments(assignment, stride=K, rows=S, max_sweeps=refine)
-        return Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats)
+            return lns(Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats))
 
     @torch.no_grad()
     def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0, constraints=None,
-                 restarts=0):
+                 restarts=0, lns_rounds=0, lns_free=12, lns_mode="targets"):
         """The non-learned yardstick for the same objective: the scenes solve() would run (scene for
         scene under the same `seed`), no policy launch, the best-response local search started from
         the empty assignment (a greedy constructor plus local search). Returns an Allocation whose
@@ -340,8 +380,11 @@ class AllocationSolver:
         holds the committed UAVs' fixed ids and nothing else, refine_stats [S, 8].
         restarts = R > 0: uavhip_search_multistart with R replicas -- replica 0 the search this call would
         run without it, the others from random full assignments drawn with Philox key `seed` -- and the
-        best J per scene, refine_stats [S, 10]. restarts = 0 launches nothing new and changes no result."""
-        exchanges, restarts = int(exchanges), int(restarts)
+        best J per scene, refine_stats [S, 10]. restarts = 0 launches nothing new and changes no result.
+        lns_rounds = L > 0: then L rounds of the large-neighbourhood search from that result, as solve's;
+        lns_J_before is the J going in. lns_rounds = 0 launches nothing more and changes nothing."""
+        exchanges, restarts, lns_rounds, lns_free = int(exchanges), int(restarts), int(lns_rounds), int(lns_free)
+        _check_lns("baseline", lns_rounds, lns_free, lns_mode)
         if exchanges < 0:
             raise ValueError("baseline: exchanges must be >= 0")
         if not 0 <= restarts <= _lib.MULTISTART_MAX_R:
@@ -370,7 +413,8 @@ class AllocationSolver:
                 assignment, J, covered, stats = env.refine_assignments(None, stride=K, rows=S, max_sweeps=max_sweeps)
             zi = torch.zeros(S, dtype=torch.int32, device=env.device)
             zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
-        return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
+            return self._lns(env, Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats), S, seed,
+                             lns_rounds, lns_free, lns_mode, allowed, capacity, fixed_ids)
 
     @torch.no_grad()
     def optimum(self, scenes=None, num_scenes=None, seed=None, constraints=None, max_workspace_bytes=1 << 30):
@@ -431,7 +475,18 @@ def main(argv=None):
                          "replicas of each scene plus R - K random starts (uavhip_search_multistart_from; --refine's and "
                          "--exchanges' caps, 32 where they are 0): mean_J_policy_starts, policy_start_wins, "
                          "policy_starts_beat_random")
+    ap.add_argument("--lns", type=int, default=0, metavar="ROUNDS",
+                    help="also the baseline (--exchanges' cap, or 32 when that is 0) followed by ROUNDS rounds of the "
+                         "large-neighbourhood search (uavhip_solve_exact_free on --lns-free UAVs a round): mean_J_lns, "
+                         "lns_improved; implies --baseline")
+    ap.add_argument("--lns-free", type=int, default=12, metavar="K", help="the UAVs freed per round of --lns, 1..16")
+    ap.add_argument("--lns-mode", choices=("random", "targets"), default="targets",
+                    help="how a round of --lns chooses them: by random keys, or the idle UAVs and the crews of random targets")
     a = ap.parse_args(argv)
+    if a.lns < 0:
+        ap.error("--lns must be >= 0")
+    if not 1 <= a.lns_free <= _lib.EXACT_FREE_MAX:
+        ap.error(f"--lns-free must be in [1, {_lib.EXACT_FREE_MAX}]")
     if a.exchanges < 0:
         ap.error("--exchanges must be >= 0")
     if not 0 <= a.restarts <= _lib.MULTISTART_MAX_R:
@@ -462,7 +517,7 @@ def main(argv=None):
         out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
         if a.exchanges > 0:
             out.update(mean_exchanges=float(r.refine_stats[:, 4].double().mean()))
-    if a.baseline or a.optimum or a.restarts > 0:
+    if a.baseline or a.optimum or a.restarts > 0 or a.lns > 0:
         b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
         out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
         if a.exchanges > 0:
@@ -477,6 +532,10 @@ def main(argv=None):
             out.update(mean_J_policy_starts=float(ps.J.mean()),
                        policy_start_wins=float((ps.refine_stats[:, 8] < a.samples).double().mean()),
                        policy_starts_beat_random=float((ps.J > bm.J).double().mean()))
+        if a.lns > 0:
+            bl = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges or 32, lns_rounds=a.lns,
+                                 lns_free=a.lns_free, lns_mode=a.lns_mode).cpu()
+            out.update(mean_J_lns=float(bl.J.mean()), lns_improved=float((bl.J > bl.lns_J_before).double().mean()))
     if a.optimum:
         o = solver.optimum(num_scenes=a.scenes, seed=a.seed).cpu()
         best = float(o.J.mean())
@@ -495,6 +554,8 @@ def main(argv=None):
             out.update(multistart_over_optimal=float(bm.J.mean()) / best, multistart_is_optimal=reaches(bm))
         if a.starts == "replicas":
             out.update(policy_starts_over_optimal=float(ps.J.mean()) / best, policy_starts_is_optimal=reaches(ps))
+        if a.lns > 0:
+            out.update(lns_over_optimal=float(bl.J.mean()) / best, lns_is_optimal=reaches(bl))
     print(json.dumps(out))
 
 

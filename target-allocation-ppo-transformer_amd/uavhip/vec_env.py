@@ -346,6 +346,116 @@ class VecUAVEnv:
                                      stream_handle()), "uavhip_solve_exact")
         return out, J, covered, stats
 
+    def exact_free_assignments(self, assignment=None, *, max_free, allowed=None, fixed=None, capacity=None, stride=1,
+                               rows=None, out=None, J=None, covered=None, stats=None, max_workspace_bytes=None):
+        """uavhip_solve_exact_free: exact_assignments' subset DP over a row's FREE UAVs only -- those with
+        fixed == 0, the first max_free (1..16) of them in ascending order; any further free UAV is held
+        like a fixed one -- for every N <= 64, M <= 128. A held UAV stays where `assignment` puts it (None:
+        on none) and only scales its target's value, so the row's result is the best of the (M + 1)^K
+        assignments of its K free UAVs: never below `assignment`'s J when that is feasible. Rows, stride
+        and the three constraint arrays are exact_assignments'; include/uavhip.h has the rule.
+        The workspace is the env's own tensor, kept and reused while it is large enough (so the call can
+        be captured in a graph after one eager call); max_workspace_bytes (None: all rows at once) caps it,
+        and more rows than fit run in chunks.
+        Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32, stats
+        [rows, 4] int32: invalid input ids, conflicts of the held UAVs with allowed / capacity, free UAVs
+        in the DP, free UAVs held by overflow). out may be `assignment` itself. The env is only read."""
+        fn = "exact_free_assignments"
+        stride, K = int(stride), int(max_free)
+        S = _rows_args(fn, self.E, stride, rows)
+        if not 1 <= K <= _lib.EXACT_FREE_MAX:
+            raise ValueError(f"{fn}: max_free={K} must be in [1, {_lib.EXACT_FREE_MAX}] (the subset DP takes "
+                             f"3^max_free steps a target)")
+        if fixed is not None and assignment is None:
+            raise ValueError(f"{fn}: fixed needs assignment (a held UAV keeps the target it gives)")
+        check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
+        out, J, covered, stats = _rows_bufs(S, self.N, 4, self.device, assignment, out, J, covered, stats)
+        row = int(LIB.uavhip_exact_free_workspace_bytes(min(K, self.N), self.M, 1))
+        fit = S if max_workspace_bytes is None else int(max_workspace_bytes) // row
+        if fit < 1:
+            raise ValueError(f"{fn}: max_workspace_bytes={max_workspace_bytes} holds no row (one row of "
+                             f"{min(K, self.N)} free UAVs x {self.M} targets needs {row} bytes)")
+        nbytes = row * min(S, fit)
+        ws = self.__dict__.get("_exact_free_ws")
+        if ws is None or ws.numel() < nbytes:
+            ws = self._exact_free_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(LIB.uavhip_solve_exact_free(self.desc, stride, S, K, ptr(allowed), ptr(fixed), ptr(capacity),
+                                          ptr(assignment), ptr(out), ptr(J), ptr(covered), ptr(stats), ptr(ws), nbytes,
+                                          stream_handle()), "uavhip_solve_exact_free")
+        return out, J, covered, stats
+
+    def pick_neighbourhood(self, assignment, K, mode, round, seed, fixed=None, stride=1, rows=None, out=None):
+        """uavhip_neighbourhood_pick: the free set of one round of a large-neighbourhood search, chosen
+        on device. -> fixed_out [rows, N] uint8, 1 = held: the UAVs with `fixed` != 0 always, and of the
+        others all but the first K (1..16) by the mode's Philox key under (`seed`, `round`): mode
+        "random" sorts the UAVs by their own keys; "targets" frees the idle UAVs first, then the whole
+        crews of targets in a random order (`assignment` [rows, N] int32 target ids or -1; None: all
+        idle). include/uavhip.h has the rule. The result is exact_free_assignments' `fixed`. The env is
+        only read."""
+        fn = "pick_neighbourhood"
+        stride, K, round, seed = int(stride), int(K), int(round), int(seed)
+        S = _rows_args(fn, self.E, stride, rows)
+        if not 1 <= K <= _lib.EXACT_FREE_MAX:
+            raise ValueError(f"{fn}: K={K} must be in [1, {_lib.EXACT_FREE_MAX}]")
+        if mode not in _lib.NBH:
+            raise ValueError(f"{fn}: mode must be one of {sorted(_lib.NBH)} (got {mode!r})")
+        if not 0 <= round < 2 ** 32:
+            raise ValueError(f"{fn}: round={round} must be in [0, 2^32)")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{fn}: seed={seed} must be in [0, 2^64)")
+        check_out(assignment, "assignment", torch.int32, (S, self.N), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        out = out_buf(out, "out", torch.uint8, (S, self.N), self.device)
+        check(LIB.uavhip_neighbourhood_pick(self.desc, stride, S, K, _lib.NBH[mode], round, seed, ptr(assignment),
+                                            ptr(fixed), ptr(out), stream_handle()), "uavhip_neighbourhood_pick")
+        return out
+
+    def lns_assignments(self, assignment, *, rounds, free, mode="targets", seed=0, allowed=None, fixed=None,
+                        capacity=None, stride=1, rows=None):
+        """Large-neighbourhood search on J: `rounds` times, pick_neighbourhood(K = free, mode, round r,
+        seed) chooses the row's free UAVs, exact_free_assignments solves that neighbourhood to optimality,
+        and the row keeps the new result only where its J is strictly greater than the one it holds --
+        compared on the doubles themselves, so J never decreases and is never below the start's.
+        `assignment` [rows, N] int32 target ids or -1 is the start (not written); the UAVs with `fixed`
+        != 0 never move, `allowed` / `capacity` bind the free UAVs of every round (a start that breaks
+        them is kept where held: start from a search under the same constraints). Everything is ordered
+        on the current stream with no host synchronisation; after one eager call (which sizes the env's
+        workspace) the call can be captured in a graph.
+        Returns (assignment [rows, N] int32 target ids, J [rows] f64, covered [rows] int32, improved
+        [rows] int32: the rounds that raised the row's J). The env is only read."""
+        fn = "lns_assignments"
+        rounds, K, seed, stride = int(rounds), int(free), int(seed), int(stride)
+        S = _rows_args(fn, self.E, stride, rows, rounds=rounds)
+        if not 1 <= K <= _lib.EXACT_FREE_MAX:
+            raise ValueError(f"{fn}: free={K} must be in [1, {_lib.EXACT_FREE_MAX}]")
+        if mode not in _lib.NBH:
+            raise ValueError(f"{fn}: mode must be one of {sorted(_lib.NBH)} (got {mode!r})")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{fn}: seed={seed} must be in [0, 2^64)")
+        if assignment is None:
+            raise ValueError(f"{fn}: assignment is required ([rows, N] int32 target ids or -1: the start)")
+        check_out(assignment, "assignment", torch.int32, (S, self.N), self.device)
+        check_out(allowed, "allowed", torch.uint8, (S, self.N, self.M), self.device)
+        check_out(fixed, "fixed", torch.uint8, (S, self.N), self.device)
+        check_out(capacity, "capacity", torch.int32, (S, self.M), self.device)
+        # the start scored and written as the library writes ids (an id of no target becomes -1)
+        best, bJ, bcov, _ = self.refine_assignments(assignment, stride=stride, rows=S, max_sweeps=0)
+        improved = torch.zeros(S, dtype=torch.int32, device=self.device)
+        held = torch.empty(S, self.N, dtype=torch.uint8, device=self.device)
+        new = tuple(torch.empty_like(t) for t in (best, bJ, bcov))
+        for r in range(rounds):
+            self.pick_neighbourhood(best, K, mode, r, seed, fixed=fixed, stride=stride, rows=S, out=held)
+            self.exact_free_assignments(best, max_free=K, allowed=allowed, fixed=held, capacity=capacity,
+                                        stride=stride, rows=S, out=new[0], J=new[1], covered=new[2])
+            up = new[1] > bJ
+            best = torch.where(up[:, None], new[0], best)
+            bJ = torch.where(up, new[1], bJ)
+            bcov = torch.where(up, new[2], bcov)
+            improved = improved + up.to(torch.int32)
+        return best, bJ, bcov, improved
+
     def search_assignments_multistart(self, assignment=None, allowed=None, fixed=None, capacity=None, restarts=16,
                                       seed=0, stride=1, rows=None, max_exchanges=32, max_sweeps=32, out=None, J=None,
                                       covered=None, stats=None, J_all=None, starts=None):
