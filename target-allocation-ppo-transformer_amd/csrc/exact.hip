@@ -121,9 +121,7 @@ __global__ __launch_bounds__(kWave) void k_exact_stage(uavhip_env env, int strid
     const ExactMask mk = reinterpret_cast<const ExactMask*>(rw + mask_off)[t];
 
     // lane u: 1 - P[u][t] and omega c[u] of the row's active scene
-    const long long e = (long long)(s0 + r) * stride;
-    const long long sb =
-        (env.scene_buffers == 2 ? (long long)(env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+    const long long sb = row_scene_base(env, s0 + r, stride);
     const double v = env.tgt_value[sb * M + t];
     double om = 1.0, wc = 0.0;
     if (lane < N) {
@@ -185,18 +183,12 @@ extern "C" int uavhip_solve_exact(const uavhip_env* env, int32_t env_stride, int
         return UAVHIP_EINVAL;
     }
     const ExactLayout w = exact_layout(env->N, env->M);
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < w.row_bytes) {
-        set_error("%s: workspace=%p (16-byte aligned) of %lld bytes holds no row: one row of %d x %d needs %lld "
-                  "(uavhip_exact_workspace_bytes)", fn, workspace, (long long)workspace_bytes, env->N, env->M,
-                  w.row_bytes);
-        return UAVHIP_EINVAL;
-    }
-    const long long fit = workspace_bytes / w.row_bytes;
-    const int chunk = (int)(fit < S ? fit : S);
+    if (const int rc = check_dp_workspace(fn, workspace, workspace_bytes, w.row_bytes, "uavhip_exact_workspace_bytes",
+                                          "%d x %d", env->N, env->M))
+        return rc;
     const int H = env->N > kExactLowBits ? env->N - kExactLowBits : 0;
     char* ws = static_cast<char*>(workspace);
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int R = S - s0 < chunk ? S - s0 : chunk;
+    return for_row_chunks(S, workspace_bytes / w.row_bytes, [&](int s0, int R) {
         UAVHIP_ROWS_LAUNCH(env, R, (k_exact_prepare<TPL, NCAP>), stream, *env, (int)env_stride, s0, R, allowed, fixed,
                            capacity, assignment_in, ws, w.row_bytes, w.mask_off, stats);
         for (int t = 0; t < env->M; ++t)
@@ -204,7 +196,6 @@ extern "C" int uavhip_solve_exact(const uavhip_env* env, int32_t env_stride, int
                                (int)env_stride, s0, t, (int)(t == 0), ws, w.row_bytes, w.d_bytes, w.choice_off, w.mask_off);
         UAVHIP_ROWS_LAUNCH(env, R, (k_exact_backtrack<TPL, NCAP>), stream, *env, (int)env_stride, s0, R, ws, w.row_bytes,
                            w.choice_off, assignment_out, J, covered);
-        if (const int rc = check_launch("k_exact_stage")) return rc;
-    }
-    return UAVHIP_OK;
+        return check_launch("k_exact_stage");
+    });
 }

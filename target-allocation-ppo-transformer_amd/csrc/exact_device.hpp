@@ -196,5 +196,30 @@ __device__ __forceinline__ void exact_stage_tile(int nb, unsigned Sh, int first,
     }
 }
 
+// ------------------------------------------------------------------ host: what the two entry points share
+// The caller's workspace: non-NULL, 16-byte aligned, at least one row of row_bytes. `sizer` names the
+// function that sizes it and `row` (a format and its values) the row, for the message.
+inline int check_dp_workspace(const char* fn, const void* workspace, int64_t workspace_bytes, long long row_bytes,
+                              const char* sizer, const char* row, ...) {
+    if (workspace && !((uintptr_t)workspace & 15) && workspace_bytes >= row_bytes) return UAVHIP_OK;
+    char c[64];
+    va_list ap;
+    va_start(ap, row);
+    vsnprintf(c, sizeof c, row, ap);
+    va_end(ap);
+    set_error("%s: workspace=%p (16-byte aligned) of %lld bytes holds no row: one row of %s needs %lld (%s)", fn,
+              workspace, (long long)workspace_bytes, c, row_bytes, sizer);
+    return UAVHIP_EINVAL;
+}
+
+// body(s0, R) on the S rows in chunks of the `fit` >= 1 rows the workspace holds; the first failure ends it
+template <class Body>
+inline int for_row_chunks(int S, long long fit, Body body) {
+    const int chunk = (int)(fit < S ? fit : S);
+    for (int s0 = 0; s0 < S; s0 += chunk)
+        if (const int rc = body(s0, S - s0 < chunk ? S - s0 : chunk)) return rc;
+    return UAVHIP_OK;
+}
+
 }  // namespace
 }  // namespace uavhip

@@ -161,9 +161,7 @@ __global__ __launch_bounds__(kWave) void k_exact_free_stage(uavhip_env env, int 
     const FreeTarget tg = reinterpret_cast<const FreeTarget*>(rw + tgt_off)[t];
 
     // lane b: 1 - P[u][t] and omega c[u] of the UAV u of bit b; 1.0 and 0.0 for a dead bit
-    const long long e = (long long)(s0 + r) * stride;
-    const long long sb =
-        (env.scene_buffers == 2 ? (long long)(env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+    const long long sb = row_scene_base(env, s0 + r, stride);
     double om = 1.0, wc = 0.0;
     if (lane < K) {
         const int u = reinterpret_cast<const uint8_t*>(rw + list_off)[lane];
@@ -206,13 +204,7 @@ __global__ __launch_bounds__(64 * kRefineWaves) void k_exact_free_backtrack(
 
 // ------------------------------------------------------------------ the neighbourhood of a round
 // One wave per row. Lane u holds UAV u's key, lane t (and t + 64) the targets' keys; a rank is a count
-// over readlanes, so nothing is sorted in memory.
-__device__ __forceinline__ uint32_t philox_word(uint32_t index, uint32_t round, uint32_t s, uint32_t stream,
-                                                uint32_t key0, uint32_t key1) {
-    const u32x4 x = philox(u32x4{index >> 2, round, s, stream}, key0, key1);
-    return (index & 2) ? ((index & 1) ? x.w : x.z) : ((index & 1) ? x.y : x.x);
-}
-
+// over readlanes, so nothing is sorted in memory. The keys are philox_word's (refine_device.hpp).
 template <int TPL>
 __global__ __launch_bounds__(64 * kRefineWaves) void k_neighbourhood_pick(
     uavhip_env env, int stride, int S, int K, int mode, uint32_t round, uint32_t key0, uint32_t key1, const int* ain,
@@ -286,18 +278,12 @@ extern "C" int uavhip_solve_exact_free(const uavhip_env* env, int32_t env_stride
     }
     const int K = max_free < env->N ? max_free : env->N;  // more bits than UAVs would all be dead
     const FreeLayout w = free_layout(K, env->M);
-    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < w.row_bytes) {
-        set_error("%s: workspace=%p (16-byte aligned) of %lld bytes holds no row: one row of %d free UAVs x %d targets "
-                  "needs %lld (uavhip_exact_free_workspace_bytes)", fn, workspace, (long long)workspace_bytes, K, env->M,
-                  w.row_bytes);
-        return UAVHIP_EINVAL;
-    }
-    const long long fit = workspace_bytes / w.row_bytes;
-    const int chunk = (int)(fit < S ? fit : S);
+    if (const int rc = check_dp_workspace(fn, workspace, workspace_bytes, w.row_bytes,
+                                          "uavhip_exact_free_workspace_bytes", "%d free UAVs x %d targets", K, env->M))
+        return rc;
     const int H = K > kExactLowBits ? K - kExactLowBits : 0;
     char* ws = static_cast<char*>(workspace);
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-        const int R = S - s0 < chunk ? S - s0 : chunk;
+    return for_row_chunks(S, workspace_bytes / w.row_bytes, [&](int s0, int R) {
         UAVHIP_ROWS_LAUNCH(env, R, (k_exact_free_prepare<TPL, NCAP>), stream, *env, (int)env_stride, s0, R, K, allowed,
                            fixed, capacity, assignment_in, ws, w.row_bytes, w.tgt_off, w.list_off, stats);
         for (int t = 0; t < env->M; ++t)
@@ -306,9 +292,8 @@ extern "C" int uavhip_solve_exact_free(const uavhip_env* env, int32_t env_stride
                                w.tgt_off, w.list_off);
         UAVHIP_ROWS_LAUNCH(env, R, (k_exact_free_backtrack<TPL, NCAP>), stream, *env, (int)env_stride, s0, R, K, fixed,
                            assignment_in, ws, w.row_bytes, w.choice_off, assignment_out, J, covered);
-        if (const int rc = check_launch("k_exact_free_stage")) return rc;
-    }
-    return UAVHIP_OK;
+        return check_launch("k_exact_free_stage");
+    });
 }
 
 extern "C" int uavhip_neighbourhood_pick(const uavhip_env* env, int32_t env_stride, int32_t S, int32_t K, int32_t mode,

@@ -41,6 +41,19 @@ __device__ __forceinline__ double wave_sum(double x) {
     return x;
 }
 
+// element base of the active scene of the row's env, s * stride: buffer istate[SCENE_SEL] (env_device.hpp)
+__device__ __forceinline__ long long row_scene_base(const uavhip_env& env, int s, int stride) {
+    const long long e = (long long)s * stride;
+    return (env.scene_buffers == 2 ? (long long)(env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+}
+
+// word `index` & 3 of the Philox4x32-10 block of counter {index >> 2, round, s, stream}
+__device__ __forceinline__ uint32_t philox_word(uint32_t index, uint32_t round, uint32_t s, uint32_t stream,
+                                                uint32_t key0, uint32_t key1) {
+    const u32x4 x = philox(u32x4{index >> 2, round, s, stream}, key0, key1);
+    return (index & 2) ? ((index & 1) ? x.w : x.z) : ((index & 1) ? x.y : x.x);
+}
+
 // What uavhip_search_assignments_constrained adds to a row (LIM): lane t holds, per target slot, the
 // UAVs that may take it and its capacity; `fixed` is wave-uniform. RefineRow's default holds nothing
 // and its sweeps are the unconstrained ones, instruction for instruction.
@@ -73,9 +86,7 @@ struct RefineRow {
         N = env.N;
         M = env.M;
         lane = lane_;
-        const long long e = (long long)s * stride;
-        const long long sb =
-            (env.scene_buffers == 2 ? (long long)(env.istate[e * UAVHIP_IST_COUNT + UAVHIP_IST_SCENE_SEL] & 1) * env.E : 0) + e;
+        const long long sb = row_scene_base(env, s, stride);
         omega = env.prm[UAVHIP_PRM_OMEGA];
         pd = env.p_dmg + sb * N * M;
 #pragma unroll

@@ -7,8 +7,9 @@
 //
 // One wave per row, four per workgroup; the row's registers and the sweeps are RefineRow
 // (refine_device.hpp), k_refine's own; the scan over the pairs is best_exchange
-// (search_device.hpp), which k_search_constrained (search_constrained.hip) runs too. No LDS, no
-// atomics, nothing shared between waves; the env and the scene are only read.
+// (search_device.hpp), which k_search_constrained (search_constrained.hip) runs too, and the loop of
+// phases and exchanges is search_loop_body.hpp, theirs as well. No LDS, no atomics, nothing shared
+// between waves; the env and the scene are only read.
 #include "search_device.hpp"
 
 namespace uavhip {
@@ -25,23 +26,7 @@ __global__ __launch_bounds__(64 * kRefineWaves) void k_search(uavhip_env env, in
     r.load(env, s, stride, lane);
     r.convert(ain, s);
     r.load_columns();
-    int exchanges = 0, scan_clean = 0;
-    for (;;) {
-        r.phase(max_sweeps);
-        if (max_exchanges == 0) break;
-        double bd;
-        int bi, bj;
-        best_exchange(r, bd, bi, bj);
-        if (!(bd > 0.0)) {
-            scan_clean = 1;
-            break;
-        }
-        if (exchanges == max_exchanges) break;
-        const int ai = readlane_i(r.a, bi), aj = readlane_i(r.a, bj);
-        if (lane == bi) r.a = aj;
-        if (lane == bj) r.a = ai;
-        ++exchanges;
-    }
+#include "search_loop_body.hpp"
 
     r.finish(s, aout, J, covered);
     if (stats && lane < 6)

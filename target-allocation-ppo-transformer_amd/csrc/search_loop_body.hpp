@@ -1,9 +1,10 @@
-// search_loop_body.hpp -- the loop of phases, scans and exchanges of the constrained searches, as
-// statements: included INSIDE the body of k_search_constrained (search_constrained.hip) and of
-// k_search_multistart (search_multistart.hip), once each, so that both run one text. (As a function
-// on RefineRow the loop compiled to different code in k_search_constrained, by reference and by value
-// alike; this form leaves that object byte for byte what it was.)
-// Reads r (RefineRow<.., true>, after start_limits and load_columns), lane, max_exchanges, max_sweeps;
+// search_loop_body.hpp -- the loop of phases, scans and exchanges of the exchange searches, as
+// statements: included INSIDE the body of k_search (search.hip), of k_search_constrained
+// (search_constrained.hip) and of k_search_multistart (search_multistart.hip), once each, so that all
+// three run one text. (As a function on RefineRow the loop compiled to different code in
+// k_search_constrained, by reference and by value alike; this form leaves that object byte for byte
+// what it was.)
+// Reads r (RefineRow, after load_columns and, with LIM, start_limits), lane, max_exchanges, max_sweeps;
 // defines exchanges and scan_clean (1: the last scan found no improving pair).
 int exchanges = 0, scan_clean = 0;
 for (;;) {

@@ -62,13 +62,14 @@ improved, and with --optimum lns_over_optimal and lns_is_optimal).
 The solver owns its env, ring buffer and sampling counters: a training RolloutEngine on the same
 policy is not touched (the packed weights are shared through policy.packed_weights()).
 """
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, fields, replace
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from .assign import _check_free, _check_mode
 from .config import cfg as default_cfg
 from .policy import rowproj_buffer
 from .vec_env import SCENE_KEYS_F64, VecUAVEnv
@@ -86,8 +87,7 @@ class Allocation:
     steps: torch.Tensor         # [S] int32: decode steps of the chosen replica
     replica_J: torch.Tensor     # [S, K] f64: J of every replica as decoding left it
     actions: Optional[torch.Tensor] = None  # [max_steps, S * K] int8 action trace (trace=True)
-    start_J: Optional[torch.Tensor] = None  # [S, R] f64: J of every replica of the search (starts="replicas");
-    #                                         placed here so that decoded_J and refine_stats stay the last two fields
+    start_J: Optional[torch.Tensor] = None  # [S, R] f64: J of every replica of the search (starts="replicas")
     lns_J_before: Optional[torch.Tensor] = None  # [S] f64: J going into the large-neighbourhood search (lns_rounds > 0)
     decoded_J: Optional[torch.Tensor] = None     # [S] f64: J before refinement (solve(refine > 0))
     refine_stats: Optional[torch.Tensor] = None  # [S, 4] int32: sweeps, moves, converged, invalid ids;
@@ -96,9 +96,7 @@ class Allocation:
     #                                              [S, 10] with restarts > 0: + the chosen replica, replicas above replica 0
 
     def cpu(self):
-        return Allocation(*(None if t is None else t.cpu() for t in
-                            (self.assignment, self.J, self.covered, self.best_replica, self.steps, self.replica_J,
-                             self.actions, self.start_J, self.lns_J_before, self.decoded_J, self.refine_stats)))
+        return Allocation(*(None if t is None else t.cpu() for t in (getattr(self, f.name) for f in fields(self))))
 
 
 @dataclass
@@ -128,19 +126,13 @@ class Constraints:
                      .contiguous() for t in out)
 
 
-def _check_constraints(what, constraints):
-    if constraints is not None and not isinstance(constraints, Constraints):
-        raise ValueError(f"{what}: constraints must be a uavhip.solve.Constraints (got {type(constraints).__name__})")
-
-
 def _check_lns(what, rounds, free, mode):
     """The lns_* arguments of solve / baseline, before any device call."""
     if rounds < 0:
         raise ValueError(f"{what}: lns_rounds must be >= 0")
-    if rounds > 0 and not 1 <= free <= _lib.EXACT_FREE_MAX:
-        raise ValueError(f"{what}: lns_free={free} must be in [1, {_lib.EXACT_FREE_MAX}]")
-    if rounds > 0 and mode not in _lib.NBH:
-        raise ValueError(f"{what}: lns_mode must be one of {sorted(_lib.NBH)} (got {mode!r})")
+    if rounds > 0:
+        _check_free(what, "lns_free", free)
+        _check_mode(what, mode, "lns_mode")
 
 
 def _with_fixed(assignment, fixed_ids, shape, device):
@@ -149,7 +141,8 @@ def _with_fixed(assignment, fixed_ids, shape, device):
         return assignment, None
     if assignment is None:
         assignment = torch.full(shape, -1, dtype=torch.int32, device=device)
-    return torch.where(fixed_ids != -2, fixed_ids, assignment), (fixed_ids != -2).to(torch.uint8)
+    ids = fixed_ids if assignment.dim() == 2 else fixed_ids[:, None]  # [S, K, N] starts: over every one of the K
+    return torch.where(ids != -2, ids, assignment), (fixed_ids != -2).to(torch.uint8)
 
 
 class AllocationSolver:
@@ -219,18 +212,6 @@ class AllocationSolver:
                 t.copy_(t[:S].repeat_interleave(K, dim=0))
         env.istate.zero_()
 
-    @staticmethod
-    def _scene_args(what, scenes, num_scenes, seed):
-        """The scene arguments of solve / baseline checked: (scenes list or None, S, seed)."""
-        if (scenes is None) == (num_scenes is None):
-            raise ValueError(f"{what}: pass scenes or num_scenes")
-        if isinstance(scenes, dict):
-            scenes = [scenes]
-        S = len(scenes) if scenes is not None else int(num_scenes)
-        if S <= 0:
-            raise ValueError(f"{what}: no scenes")
-        return scenes, S, 0 if seed is None else int(seed)
-
     def _scene_env(self, scenes, S, seed):
         """The env of S * K replicas with the scenes in place (the solver's device current)."""
         env = self._size(S)
@@ -240,11 +221,71 @@ class AllocationSolver:
             self._generate_scenes(env, S, seed)
         return env
 
-    def _lns(self, env, alloc, S, seed, rounds, free, mode, allowed, capacity, fixed_ids):
+    def _prepare(self, what, scenes, num_scenes, seed, constraints, refusals=()):
+        """The arguments solve / baseline / optimum (`what`) share, checked before anything is allocated; the caller's
+        own (refused, message) pairs come between the constraints' type and the scene arguments. -> (scenes list or
+        None, S, seed, limits: (allowed, capacity, fixed_ids) on the solver's device, None without constraints)."""
+        if constraints is not None and not isinstance(constraints, Constraints):
+            raise ValueError(f"{what}: constraints must be a uavhip.solve.Constraints (got {type(constraints).__name__})")
+        for refused, message in refusals:
+            if refused:
+                raise ValueError(message)
+        if (scenes is None) == (num_scenes is None):
+            raise ValueError(f"{what}: pass scenes or num_scenes")
+        if isinstance(scenes, dict):
+            scenes = [scenes]
+        S = len(scenes) if scenes is not None else int(num_scenes)
+        if S <= 0:
+            raise ValueError(f"{what}: no scenes")
+        limits = None if constraints is None else constraints.on(what, S, self.N, self.M, self.device)
+        return scenes, S, 0 if seed is None else int(seed), limits
+
+    def _undecoded(self, env, S, assignment, J, covered, stats):
+        """The Allocation of baseline / optimum: the decode-only fields (best_replica, steps, replica_J) zeros."""
+        zi = torch.zeros(S, dtype=torch.int32, device=env.device)
+        return Allocation(assignment, J, covered, zi, zi.clone(),
+                          torch.zeros(S, self.K, dtype=torch.float64, device=env.device), refine_stats=stats)
+
+    def _decode(self, env, S, seed, max_steps, trace):
+        """The scenes in `env` decoded, K replicas each, and the best replica chosen: solve(refine=0)'s Allocation."""
+        K = self.K
+        n_max = int(self.N * self.M if max_steps is None else max_steps)
+        actions = torch.empty(n_max, env.E, dtype=torch.int8, device=env.device) if trace else None
+        self.steps.zero_()
+        self.ep_return.zero_()
+        env.reset(episode=1, obs_out=self.obs2[0])
+        self.policy.packed_weights()
+        self.policy.decode_steps(env, self.obs2, self.rowproj, 0, True, self.steps, self.finished, actions=actions,
+                                 ep_return=self.ep_return, n_max=n_max, greedy_stride=K, seed=seed, offset=0,
+                                 offset_stride=env.E)
+        best, J, covered, assignment = env.select_best(K)
+        replica_J = env.dstate[:, _lib.DST["J"]].reshape(S, K).clone()
+        steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
+        return Allocation(assignment, J, covered, best, steps, replica_J, actions)
+
+    def _search(self, env, start, S, sweeps, exchanges, restarts, seed, limits):
+        """The one search solve / baseline launch on S scenes from `start` [S, N] (None: the empty
+        assignment): the multi-start with restarts > 0, else the constrained search under `limits`, else
+        the exchange search with exchanges > 0, else the plain refinement. The first two lay the committed
+        UAVs' ids over the start. -> (assignment, J, covered, stats)."""
+        rows = dict(stride=self.K, rows=S, max_sweeps=sweeps)
+        if restarts == 0 and limits is None:
+            if exchanges > 0:
+                return env.search_assignments(start, max_exchanges=exchanges, **rows)
+            return env.refine_assignments(start, **rows)
+        allowed, capacity, fixed_ids = limits or (None, None, None)
+        start, fixed = _with_fixed(start, fixed_ids, (S, self.N), env.device)
+        if restarts > 0:
+            return env.search_assignments_multistart(start, allowed, fixed, capacity, restarts=restarts,
+                                                     seed=seed & (2 ** 64 - 1), max_exchanges=exchanges, **rows)
+        return env.search_assignments_constrained(start, allowed, fixed, capacity, max_exchanges=exchanges, **rows)
+
+    def _lns(self, env, alloc, S, seed, rounds, free, mode, limits):
         """`alloc` after `rounds` rounds of the large-neighbourhood search from its assignment, the
         committed UAVs held; alloc itself when rounds == 0."""
         if rounds == 0:
             return alloc
+        allowed, capacity, fixed_ids = limits or (None, None, None)
         fixed = None if fixed_ids is None else (fixed_ids != -2).to(torch.uint8)
         assignment, J, covered, _ = env.lns_assignments(alloc.assignment, rounds=rounds, free=free, mode=mode,
                                                         seed=seed & (2 ** 64 - 1), allowed=allowed, fixed=fixed,
@@ -308,65 +349,33 @@ class AllocationSolver:
             raise ValueError("solve: exchanges must be >= 0")
         if exchanges > 0 and refine == 0:
             raise ValueError("solve: exchanges > 0 needs refine > 0 (the sweeps between the exchanges)")
-        _check_constraints("solve", constraints)
-        if constraints is not None and refine == 0:
-            raise ValueError("solve: constraints need refine > 0 (the decode ignores them; the search applies them)")
-        lns = lambda alloc: self._lns(env, alloc, S, seed, lns_rounds, lns_free, lns_mode, allowed, capacity,  # noqa: E731
-                                      fixed_ids)
-        if starts == "replicas":
-            if self.K < 2:
-                raise ValueError(f"solve: starts='replicas' needs samples >= 2 (got {self.K}: one replica is starts='best')")
-            if restarts < self.K:
-                raise ValueError(f"solve: starts='replicas' needs restarts={restarts} >= samples={self.K} "
-                                 f"(one replica of the search per decoded replica)")  # so restarts > 0: refine > 0
-        scenes, S, seed = self._scene_args("solve", scenes, num_scenes, seed)
         K = self.K
-        allowed = capacity = fixed_ids = None
-        if constraints is not None:
-            allowed, capacity, fixed_ids = constraints.on("solve", S, self.N, self.M, self.device)
+        scenes, S, seed, limits = self._prepare("solve", scenes, num_scenes, seed, constraints, (
+            (constraints is not None and refine == 0,
+             "solve: constraints need refine > 0 (the decode ignores them; the search applies them)"),
+            (starts == "replicas" and K < 2,
+             f"solve: starts='replicas' needs samples >= 2 (got {K}: one replica is starts='best')"),
+            (starts == "replicas" and restarts < K,  # so restarts > 0: refine > 0
+             f"solve: starts='replicas' needs restarts={restarts} >= samples={K} (one replica of the search per "
+             f"decoded replica)")))
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
-            n_max = int(self.N * self.M if max_steps is None else max_steps)
-            actions = torch.empty(n_max, env.E, dtype=torch.int8, device=env.device) if trace else None
-            self.steps.zero_()
-            self.ep_return.zero_()
-            env.reset(episode=1, obs_out=self.obs2[0])
-            self.policy.packed_weights()
-            self.policy.decode_steps(env, self.obs2, self.rowproj, 0, True, self.steps, self.finished, actions=actions,
-                                     ep_return=self.ep_return, n_max=n_max, greedy_stride=K, seed=seed, offset=0,
-                                     offset_stride=env.E)
-            best, J, covered, assignment = env.select_best(K)
-            replica_J = env.dstate[:, _lib.DST["J"]].reshape(S, K).clone()
-            steps = torch.gather(self.steps.view(S, K), 1, best.clamp(min=0).long().view(S, 1)).view(S)
-            if refine == 0:
-                return lns(Allocation(assignment, J, covered, best, steps, replica_J, actions))
-            if starts == "replicas":
+            r = self._decode(env, S, seed, max_steps, trace)
+            start_J = None
+            if refine > 0 and starts == "replicas":
+                allowed, capacity, fixed_ids = limits or (None, None, None)
                 given = env.assigned_target_ids().to(torch.int32).view(S, K, self.N)  # scene-major already: no gather
-                fixed = None
-                if fixed_ids is not None:
-                    given, fixed = _with_fixed(given, fixed_ids.view(S, 1, self.N), None, env.device)
-                    fixed = fixed.view(S, self.N)
+                given, fixed = _with_fixed(given, fixed_ids, None, env.device)
                 start_J = torch.empty(S, restarts, dtype=torch.float64, device=env.device)
-                refined, rJ, rcov, stats = env.search_assignments_multistart(
+                found = env.search_assignments_multistart(
                     None, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
                     max_exchanges=exchanges, max_sweeps=refine, J_all=start_J, starts=given.contiguous())
-                return lns(Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J,
-                                      refine_stats=stats, start_J=start_J))
-            if restarts > 0:
-                start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
-                refined, rJ, rcov, stats = env.search_assignments_multistart(
-                    start, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
-                    max_exchanges=exchanges, max_sweeps=refine)
-            elif constraints is not None:
-                start, fixed = _with_fixed(assignment, fixed_ids, (S, self.N), env.device)
-                refined, rJ, rcov, stats = env.search_assignments_constrained(
-                    start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=refine)
-            elif exchanges > 0:
-                refined, rJ, rcov, stats = env.search_assignments(assignment, stride=K, rows=S, max_exchanges=exchanges,
-                                                                  max_sweeps=refine)
-            else:
-                refined, rJ, rcov, stats = env.refine_assignments(assignment, stride=K, rows=S, max_sweeps=refine)
-            return lns(Allocation(refined, rJ, rcov, best, steps, replica_J, actions, decoded_J=J, refine_stats=stats))
+            elif refine > 0:
+                found = self._search(env, r.assignment, S, refine, exchanges, restarts, seed, limits)
+            if refine > 0:
+                r = replace(r, assignment=found[0], J=found[1], covered=found[2], decoded_J=r.J, refine_stats=found[3],
+                            start_J=start_J)
+            return self._lns(env, r, S, seed, lns_rounds, lns_free, lns_mode, limits)
 
     @torch.no_grad()
     def baseline(self, scenes=None, num_scenes=None, seed=None, max_sweeps=32, exchanges=0, constraints=None,
@@ -389,32 +398,11 @@ class AllocationSolver:
             raise ValueError("baseline: exchanges must be >= 0")
         if not 0 <= restarts <= _lib.MULTISTART_MAX_R:
             raise ValueError(f"baseline: restarts must be in [0, {_lib.MULTISTART_MAX_R}]")
-        _check_constraints("baseline", constraints)
-        scenes, S, seed = self._scene_args("baseline", scenes, num_scenes, seed)
-        K = self.K
-        allowed = capacity = fixed_ids = None
-        if constraints is not None:
-            allowed, capacity, fixed_ids = constraints.on("baseline", S, self.N, self.M, self.device)
+        scenes, S, seed, limits = self._prepare("baseline", scenes, num_scenes, seed, constraints)
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
-            if restarts > 0:
-                start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
-                assignment, J, covered, stats = env.search_assignments_multistart(
-                    start, allowed, fixed, capacity, restarts=restarts, seed=seed & (2 ** 64 - 1), stride=K, rows=S,
-                    max_exchanges=exchanges, max_sweeps=max_sweeps)
-            elif constraints is not None:
-                start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
-                assignment, J, covered, stats = env.search_assignments_constrained(
-                    start, allowed, fixed, capacity, stride=K, rows=S, max_exchanges=exchanges, max_sweeps=max_sweeps)
-            elif exchanges > 0:
-                assignment, J, covered, stats = env.search_assignments(None, stride=K, rows=S, max_exchanges=exchanges,
-                                                                       max_sweeps=max_sweeps)
-            else:
-                assignment, J, covered, stats = env.refine_assignments(None, stride=K, rows=S, max_sweeps=max_sweeps)
-            zi = torch.zeros(S, dtype=torch.int32, device=env.device)
-            zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
-            return self._lns(env, Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats), S, seed,
-                             lns_rounds, lns_free, lns_mode, allowed, capacity, fixed_ids)
+            found = self._search(env, None, S, max_sweeps, exchanges, restarts, seed, limits)
+            return self._lns(env, self._undecoded(env, S, *found), S, seed, lns_rounds, lns_free, lns_mode, limits)
 
     @torch.no_grad()
     def optimum(self, scenes=None, num_scenes=None, seed=None, constraints=None, max_workspace_bytes=1 << 30):
@@ -424,22 +412,16 @@ class AllocationSolver:
         decode-only fields are zeros, as baseline's; refine_stats is [S, 2]: invalid ids, fixed conflicts.
         constraints = Constraints(...): the maximum over the allocations baseline(constraints=) may end
         on -- committed UAVs where they are, allowed pairs only, capacities kept."""
-        _check_constraints("optimum", constraints)
-        if self.N > _lib.EXACT_MAX_N:
-            raise ValueError(f"optimum: N={self.N} > {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)")
-        scenes, S, seed = self._scene_args("optimum", scenes, num_scenes, seed)
-        K = self.K
-        allowed = capacity = fixed_ids = None
-        if constraints is not None:
-            allowed, capacity, fixed_ids = constraints.on("optimum", S, self.N, self.M, self.device)
+        scenes, S, seed, limits = self._prepare("optimum", scenes, num_scenes, seed, constraints, ((
+            self.N > _lib.EXACT_MAX_N,
+            f"optimum: N={self.N} > {_lib.EXACT_MAX_N} (the subset DP takes 3^N steps a target)"),))
+        allowed, capacity, fixed_ids = limits or (None, None, None)
         with torch.cuda.device(self.device):
             env = self._scene_env(scenes, S, seed)
             start, fixed = _with_fixed(None, fixed_ids, (S, self.N), env.device)
-            assignment, J, covered, stats = env.exact_assignments(start, allowed, fixed, capacity, stride=K, rows=S,
-                                                                  max_workspace_bytes=max_workspace_bytes)
-            zi = torch.zeros(S, dtype=torch.int32, device=env.device)
-            zJ = torch.zeros(S, K, dtype=torch.float64, device=env.device)
-        return Allocation(assignment, J, covered, zi, zi.clone(), zJ, refine_stats=stats)
+            found = env.exact_assignments(start, allowed, fixed, capacity, stride=self.K, rows=S,
+                                          max_workspace_bytes=max_workspace_bytes)
+            return self._undecoded(env, S, *found)
 
 
 def main(argv=None):
@@ -501,11 +483,12 @@ def main(argv=None):
     policy = TransformerActorCritic().to(dev)
     load_checkpoint(policy, a.checkpoint)
     solver = AllocationSolver(policy, a.uavs, a.targets, samples=a.samples)
+    on = dict(num_scenes=a.scenes, seed=a.seed)
     ex = a.exchanges if a.refine > 0 else 0  # without --refine, --exchanges is the baseline's alone
-    solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine, exchanges=ex)  # warm-up: allocation, weight pack
+    solver.solve(**on, refine=a.refine, exchanges=ex)  # warm-up: allocation, weight pack
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine, exchanges=ex)
+    r = solver.solve(**on, refine=a.refine, exchanges=ex)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     r = r.cpu()
@@ -517,45 +500,40 @@ def main(argv=None):
         out.update(mean_J_decoded=float(r.decoded_J.mean()), mean_J_refined=float(r.J.mean()))
         if a.exchanges > 0:
             out.update(mean_exchanges=float(r.refine_stats[:, 4].double().mean()))
+    rivals = {}  # name -> Allocation: what --optimum reports as name_over_optimal and name_is_optimal, in this order
     if a.baseline or a.optimum or a.restarts > 0 or a.lns > 0:
-        b = solver.baseline(num_scenes=a.scenes, seed=a.seed).cpu()
+        b = solver.baseline(**on).cpu()
         out.update(mean_J_baseline=float(b.J.mean()), policy_beats_baseline=float((r.J > b.J).double().mean()))
         if a.exchanges > 0:
-            bx = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges).cpu()
+            bx = rivals["baseline_exchange"] = solver.baseline(**on, exchanges=a.exchanges).cpu()
             out.update(mean_J_baseline_exchange=float(bx.J.mean()))
         if a.restarts > 0:
-            bm = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges or 32, restarts=a.restarts).cpu()
+            bm = rivals["multistart"] = solver.baseline(**on, exchanges=a.exchanges or 32, restarts=a.restarts).cpu()
             out.update(mean_J_multistart=float(bm.J.mean()))
         if a.starts == "replicas":
-            ps = solver.solve(num_scenes=a.scenes, seed=a.seed, refine=a.refine or 32, exchanges=a.exchanges or 32,
-                              restarts=a.restarts, starts="replicas").cpu()
+            ps = rivals["policy_starts"] = solver.solve(**on, refine=a.refine or 32, exchanges=a.exchanges or 32,
+                                                        restarts=a.restarts, starts="replicas").cpu()
             out.update(mean_J_policy_starts=float(ps.J.mean()),
                        policy_start_wins=float((ps.refine_stats[:, 8] < a.samples).double().mean()),
                        policy_starts_beat_random=float((ps.J > bm.J).double().mean()))
         if a.lns > 0:
-            bl = solver.baseline(num_scenes=a.scenes, seed=a.seed, exchanges=a.exchanges or 32, lns_rounds=a.lns,
-                                 lns_free=a.lns_free, lns_mode=a.lns_mode).cpu()
+            bl = rivals["lns"] = solver.baseline(**on, exchanges=a.exchanges or 32, lns_rounds=a.lns, lns_free=a.lns_free,
+                                                 lns_mode=a.lns_mode).cpu()
             out.update(mean_J_lns=float(bl.J.mean()), lns_improved=float((bl.J > bl.lns_J_before).double().mean()))
     if a.optimum:
-        o = solver.optimum(num_scenes=a.scenes, seed=a.seed).cpu()
+        o = solver.optimum(**on).cpu()
         best = float(o.J.mean())
 
-        def reaches(x):
-            return float((x.J >= o.J - RTOL * o.J.abs().clamp(min=1.0)).double().mean())
-        out.update(mean_J_optimal=best, baseline_over_optimal=float(b.J.mean()) / best)
+        over = lambda J: float(J.mean()) / best  # noqa: E731
+        reaches = lambda x: float((x.J >= o.J - RTOL * o.J.abs().clamp(min=1.0)).double().mean())  # noqa: E731
+        out.update(mean_J_optimal=best, baseline_over_optimal=over(b.J))
         if a.refine > 0:
-            out.update(decoded_over_optimal=float(r.decoded_J.mean()) / best, refined_over_optimal=float(r.J.mean()) / best)
+            out.update(decoded_over_optimal=over(r.decoded_J), refined_over_optimal=over(r.J))
         else:
-            out.update(decoded_over_optimal=float(r.J.mean()) / best)
+            out.update(decoded_over_optimal=over(r.J))
         out.update(baseline_is_optimal=reaches(b))
-        if a.exchanges > 0:
-            out.update(baseline_exchange_over_optimal=float(bx.J.mean()) / best, baseline_exchange_is_optimal=reaches(bx))
-        if a.restarts > 0:
-            out.update(multistart_over_optimal=float(bm.J.mean()) / best, multistart_is_optimal=reaches(bm))
-        if a.starts == "replicas":
-            out.update(policy_starts_over_optimal=float(ps.J.mean()) / best, policy_starts_is_optimal=reaches(ps))
-        if a.lns > 0:
-            out.update(lns_over_optimal=float(bl.J.mean()) / best, lns_is_optimal=reaches(bl))
+        for name, x in rivals.items():
+            out.update({f"{name}_over_optimal": over(x.J), f"{name}_is_optimal": reaches(x)})
     print(json.dumps(out))
 
 
